@@ -16,10 +16,19 @@ cost-balanced row stripe of ~13.4k pairs; each step ends with ONE all-gather of 
 (RCCL over xGMI) that assembles the full N x N score matrix on every rank. value = all
 pairs of all ranks / max-over-ranks time.
 
-Also reported: roofline of the path (SURVEY.md §8d ops_pair) with per-kernel HIP-event
-times, MAP/MR1 of the assembled matrix (reference normalisation + evaluation), and the CPU
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, the configuration and the build id). --dump-outputs DIR
+also writes what the last timed step returned to its caller, the assembled (tracks x tracks)
+float32 Qmax score matrix (upper triangle filled), as DIR/scores.npy; the corpus depends only on
+the arguments, so two builds run with the same arguments can be compared score for score.
+
+With --full also reported: roofline of the path (SURVEY.md §8d ops_pair) with per-kernel HIP-event
+times, MAP/MR1 of the assembled matrix (reference normalisation + evaluation), the CPU
 baseline: the oracle (C++ restatement, oracle/) timed on the host cores of this node over a
-bounded random sample of the same pairs, whose Qmax values are also checked for equality.
+bounded random sample of the same pairs, whose Qmax values are also checked for equality, the
+other scorers (SiMPle, EarlyFusion, SNF, the Da-TACOS stripe), and at N > 1 the per-rank exchange
+diagnostics and the SNF sharding plan. --cpu-sample, --cpu-threads, --no-profile and --no-paths
+trim a --full run and change nothing without it.
 """
 import argparse
 import json
@@ -616,9 +625,18 @@ def main():
                     help="0 = the box's CPU share (OMP_NUM_THREADS, else every CPU this process may run on)")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-paths", action="store_true", help="skip the SiMPle / EarlyFusion lines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: per-kernel roofline, "
+                         "MAP and oracle parity, CPU baselines, the other scorers, multi-GPU diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's score matrix to DIR/scores.npy (float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         return launch_ranks(args.gpus)  # before anything touches the GPU
@@ -662,12 +680,12 @@ def main():
     my_pairs = torch.as_tensor(my_pairs_np).cuda()
     total_pairs = T * (T - 1) // 2
 
-    # at N > 1 every timed step also records HIP events around its compute and its exchange on the
-    # stream they run on (no synchronisation inside the timed region), for the per-rank diagnostics
+    # with --full at N > 1 every timed step also records HIP events around its compute and its exchange
+    # on the stream they run on (no synchronisation inside the timed region), for the per-rank diagnostics
     step_events = []
 
     def step(timed=False):
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed and world > 1 else None
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed and args.full and world > 1 else None
         if evs:
             evs[0].record()
         out = bank.crp_align(my_pairs, qmax=True)
@@ -699,8 +717,13 @@ def main():
     barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the assembled score matrix (every rank holds it)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), D.cpu().numpy().astype(np.float32, copy=False))
+        log("outputs written to %s" % args.dump_outputs)
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         comp_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in step_events]))
         exch_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in step_events]))
         blk = distributed.scatter_stripe(my_pairs, bank.crp_align(my_pairs, qmax=True)["qmax"], r0, r1, T)
@@ -722,6 +745,27 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = total_pairs * args.steps / dt
+    head = {
+        "metric": "song-pairs/sec (CSM+Qmax) on 12-d HPCP, ~2000 frames/track; MAP parity",
+        "value": round(value, 2), "unit": "song-pairs/s", "n_gpus": n_gpus, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "covers80-shaped synthetic HPCP (%s corpus), Serra09 CRP+Qmax, all unordered pairs"
+                               % args.corpus,
+                   "tracks": T, "pairs_per_step": total_pairs, "frames_per_track": args.frames,
+                   "m": 9, "tau": 1, "kappa": 0.095, "oti": True, "parallelism": "pair-matrix row stripes dp%d"
+                   % n_gpus},
+        "full": bool(args.full),
+        "launch": {"world": world, "device_count": n_dev, "backend": backend if world > 1 else None,
+                   "launcher": os.environ.get("ACOSS_BENCH_LAUNCHER", "external" if world > 1 else None)},
+    }
+    if not args.full:  # the plain run ends here: the headline line and nothing measured beside it
+        if rank == 0:
+            print(json.dumps(dict(head, build=build_id())))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
 
     # ---- one call of the path timed with HIP events on the stream it is launched on ----
     # (a) as the timed steps run it (two streams: one sub-batch's selects overlap the next one's
@@ -849,26 +893,16 @@ def main():
             log("other paths (SiMPle, EarlyFusion, SNF)")
             paths = other_paths(nth, args.seed)
 
-        result = {
-            "metric": "song-pairs/sec (CSM+Qmax) on 12-d HPCP, ~2000 frames/track; MAP parity",
-            "value": round(value, 2), "unit": "song-pairs/s", "n_gpus": n_gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "covers80-shaped synthetic HPCP (%s corpus), Serra09 CRP+Qmax, all unordered pairs"
-                                   % args.corpus,
-                       "tracks": T, "pairs_per_step": total_pairs, "frames_per_track": args.frames,
-                       "m": 9, "tau": 1, "kappa": 0.095, "oti": True, "parallelism": "pair-matrix row stripes dp%d"
-                       % n_gpus},
-            "map": round(float(MAP), 6), "mr1": round(float(MR), 4), "mrr": round(float(MRR), 6),
-            "top1": int(tops[0]), "map_parity": map_parity,
-            "roofline": roofline, "cpu_baseline": cpu,
-            "speedup_vs_cpu": round(value / cpu["value"], 1) if cpu else None,
-            "other_paths": paths,
-            "build": build,
-            "launch": {"world": world, "device_count": n_dev, "backend": backend if world > 1 else None,
-                       "launcher": os.environ.get("ACOSS_BENCH_LAUNCHER", "external" if world > 1 else None)},
-            "multi_gpu": multi,
-        }
+        result = dict(
+            head,
+            map=round(float(MAP), 6), mr1=round(float(MR), 4), mrr=round(float(MRR), 6),
+            top1=int(tops[0]), map_parity=map_parity,
+            roofline=roofline, cpu_baseline=cpu,
+            speedup_vs_cpu=round(value / cpu["value"], 1) if cpu else None,
+            other_paths=paths,
+            build=build,
+            multi_gpu=multi,
+        )
     if world > 1 and not args.no_paths:
         # SNF late fusion at Da-TACOS size across the ranks: the measured sharding decision
         # (similarity_fusion.shard_plan: one replicated step vs one all-gather of B, max over ranks)

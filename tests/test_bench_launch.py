@@ -29,6 +29,16 @@ def test_world_size_mismatch_fails_loudly():
     assert r.stdout.strip() == ""  # no JSON line for a run that did not happen
 
 
+def test_plain_run_options():
+    """--full and --dump-outputs exist, and --steps must name at least one timed step (ms_per_step
+    is the time of the run divided by it); refused before anything touches torch or the GPU."""
+    r = _run(["--help"], {})
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = _run(["--gpus", "1", "--steps", "0", "--warmup", "0"], {})
+    assert r.returncode != 0 and "--steps" in r.stderr
+    assert r.stdout.strip() == ""
+
+
 def test_self_launch_propagates_rank_failure():
     # two ranks, no GPU here: every rank fails at its first GPU call; the parent must report it
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-paths", "--cpu-sample", "0"],
