@@ -8,7 +8,11 @@
 // step for step (fmaf chains, sequential adds, correctly rounded sqrt), so the OTI index,
 // the thresholds and the CRP mask are bit-identical to the CPU restatement.
 //
-// Design: nothing of size M'xN' ever touches HBM.
+// Design: two CRP paths, chosen in one place (crp_masks below). The reference's
+// setting (m = 9, tau = 1, lines of at most 4096 codes) runs the split kernels of crp_split.hip,
+// which keep the high 16 bits of every M'xN' distance key in HBM twice (row-major and
+// strip-major key planes, 4 B per cell, per sub-batch). Every other shape runs the generic
+// kernels of this file, which keep no distance in HBM: the CRP words are the only M'xN' output.
 //  * k_crp_select<TRANS>: one 256-thread block per (pair, stripe of R own frames). It
 //    sweeps the other song in 256-column panels: the 12-d Gram of (R+m-1) x (256+m-1)
 //    frames is computed into LDS (fmaf chains), the m-tap diagonal window gives the squared
@@ -983,27 +987,6 @@ int set_lds(K kernel, size_t bytes) {
   return ACOSS_OK;
 }
 
-struct Stage {
-  int R = 0;
-  size_t sel_lds = 0, pan_lds = 0;
-};
-
-int prepare_stage(int m, int ld, Stage* st) {
-  st->R = pick_R(m, ld);
-  if (st->R <= 0) {
-    set_error("track too long for the LDS stripe (stacked length %d)", ld);
-    return ACOSS_E_SHAPE;
-  }
-  st->sel_lds = select_lds_bytes(st->R, m, ld);
-  st->pan_lds = panel_lds_floats(32, m) * sizeof(float);
-  int rc;
-  if ((rc = set_lds(k_crp_select<false>, st->sel_lds))) return rc;
-  if ((rc = set_lds(k_crp_select<true>, st->sel_lds))) return rc;
-  if ((rc = set_lds(k_crp_panel<0>, st->pan_lds))) return rc;
-  if ((rc = set_lds(k_crp_panel<1>, st->pan_lds))) return rc;
-  return ACOSS_OK;
-}
-
 template <int ALIGN, int R>
 void launch_dp_r(bool eqg, int nb, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
                  float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s, int L = 0) {
@@ -1051,66 +1034,224 @@ void launch_dp(bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride, 
     launch_dp_r<ALIGN, 32>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s);
 }
 
-// Thresholds of one side: fast m=9 path (crp_select.hip) unless ACOSS_SELECT_GENERIC is set
-// or the shape is outside it; otherwise the generic LDS-Gram kernel above.
-int run_select(bool trans, const Stage& st, const CrpBatch& B, int nb, int L, int ld, float kappa, float* thr, float* T,
-               int64_t thr_stride, hipStream_t s) {
-  static const bool generic = getenv("ACOSS_SELECT_GENERIC") != nullptr;
-  if (!generic) {
-    const int rc = launch_select16(trans, B, nb, L, kappa, thr, T, thr_stride, s);
-    if (rc != 1) return rc;
-  }
-  if (trans)
-    hipLaunchKernelGGL(k_crp_select<true>, dim3((L + st.R - 1) / st.R, nb), dim3(256), st.sel_lds, s, B, st.R, ld,
-                       kappa, thr, T, thr_stride);
-  else
-    hipLaunchKernelGGL(k_crp_select<false>, dim3((L + st.R - 1) / st.R, nb), dim3(256), st.sel_lds, s, B, st.R, ld,
-                       kappa, thr, T, thr_stride);
-  ACOSS_LAUNCH_CHECK();
-  return ACOSS_OK;
-}
+// Per-track tables of one call, in workspace slot 0: prof (n_tracks x 12) | NX (n_tracks x ldn) |
+// X2, the interleaved frame pairs of the split sweep (n_tracks x ldn x 24).
+struct TrackPrep {
+  const float* feats;
+  const int64_t* off;
+  const int32_t* len;
+  float *prof, *NX, *X2;
+  int ldn;
+};
 
-// CRP words: fast m=9 kernel (crp_mask.hip) unless ACOSS_MASK_GENERIC is set.
-int run_mask(const Stage& st, const CrpBatch& B, int nb, int L, int nstrips, const float* Tr, const float* Tc,
-             int64_t thr_stride, uint32_t* maskT, int64_t mask_stride, int ld, hipStream_t s) {
-  static const bool generic = getenv("ACOSS_MASK_GENERIC") != nullptr;
-  if (!generic) {
-    const int rc = launch_mask9(B, nb, L, Tr, Tc, thr_stride, maskT, mask_stride, ld, s);
-    if (rc != 1) return rc;
-  }
-  hipLaunchKernelGGL(k_crp_panel<0>, dim3((L + kPanelW - 1) / kPanelW, nstrips, nb), dim3(256), st.pan_lds, s, B,
-                     Tr, Tc, thr_stride, maskT, mask_stride, ld, (float*)nullptr);
-  ACOSS_LAUNCH_CHECK();
-  return ACOSS_OK;
-}
-
-// Per-track prep into workspace slot 0: prof (n_tracks x 12) | NX (n_tracks x ldn) | and, when
-// X2 is requested, the interleaved frame pairs (n_tracks x ldn x 24).
 int run_prep(const float* feats, const int64_t* off, const int32_t* len, int n_tracks, int max_len, int m, int tau,
-             hipStream_t s, float** prof, float** NX, int* ldn, float** X2 = nullptr) {
+             hipStream_t s, TrackPrep* T) {
   // 32 spare frames per track: the systolic sweep's last (partial) strip reads query frames up
   // to 31 past the track's end (values unused: those rows are never stored)
-  *ldn = (int)align_up((size_t)max_len + 32, 64);
-  const size_t base = align_up((size_t)n_tracks * 12 + (size_t)n_tracks * (*ldn), 64);
-  const size_t bytes = (base + (X2 ? (size_t)n_tracks * (*ldn) * 24 : 0)) * sizeof(float);
-  float* ws = static_cast<float*>(workspace(0, bytes));
+  const int ldn = (int)align_up((size_t)max_len + 32, 64);
+  const size_t base = align_up((size_t)n_tracks * 12 + (size_t)n_tracks * ldn, 64);
+  float* ws = static_cast<float*>(workspace(0, (base + (size_t)n_tracks * ldn * 24) * sizeof(float)));
   if (!ws) return ACOSS_E_HIP;
-  *prof = ws;
-  *NX = ws + (size_t)n_tracks * 12;
-  if (X2) {
-    *X2 = ws + base;
-    if (max_len > 0) {
-      hipLaunchKernelGGL(k_track_pairs, dim3(n_tracks, (max_len + 255) / 256), dim3(256), 0, s, feats, off, len, *ldn,
-                         *X2);
-      ACOSS_LAUNCH_CHECK();
-    }
+  *T = TrackPrep{feats, off, len, ws, ws + (size_t)n_tracks * 12, ws + base, ldn};
+  if (max_len > 0) {
+    hipLaunchKernelGGL(k_track_pairs, dim3(n_tracks, (max_len + 255) / 256), dim3(256), 0, s, feats, off, len, ldn,
+                       T->X2);
+    ACOSS_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_track_profile, dim3((n_tracks + 3) / 4), dim3(64), 0, s, feats, off, len, n_tracks, *prof);
+  hipLaunchKernelGGL(k_track_profile, dim3((n_tracks + 3) / 4), dim3(64), 0, s, feats, off, len, n_tracks, T->prof);
   ACOSS_LAUNCH_CHECK();
   if (max_len > 0) {
     hipLaunchKernelGGL(k_track_norms, dim3(n_tracks, (max_len + 255) / 256), dim3(256), 0, s, feats, off, len, m,
-                       tau, *ldn, *NX);
+                       tau, ldn, T->NX);
     ACOSS_LAUNCH_CHECK();
+  }
+  return ACOSS_OK;
+}
+
+// What one CRP call derives from (m, tau, longest track, pairs): which of the two paths runs, the
+// pitches its kernels index with, and workspace slot 1 carved to them. acoss_crp_align and
+// acoss_crp_pair both get it from crp_plan and their thresholds and CRP words from crp_masks, so
+// the single pair runs the batch's kernels on the batch's buffers (the read margins the split
+// kernels rely on included).
+struct CrpPlan {
+  int m, tau, L, ld, nstrips;
+  int64_t thr_stride, mask_stride, bnd_stride, yrot_stride;
+  bool split;        // crp_split.hip (m = 9, tau = 1, lines <= 4096 codes); else the generic kernels
+  int ldk;           // key planes: row pitch
+  int64_t kstride;   // key planes: codes per pair and plane
+  int64_t nb_alloc;  // pairs per DP batch
+  int64_t sub;       // pairs per CRP sub-batch
+  int nbuf;          // key-plane buffers = streams the sub-batches rotate over
+  int R;             // generic select: own frames per block
+  size_t sel_lds, pan_lds;
+  // per pair of a DP batch: oti, dims, thr/T rows+cols, maskT, band boundary, rolled reference
+  int32_t* oti;
+  int2* dims;
+  float *thr_r, *T_r, *thr_c, *T_c;
+  uint32_t* mask;
+  float4* bnd;
+  float* yrot;
+  void* kpl[3];     // per buffer: the key planes of a sub-batch
+  uint32_t* rt[3];  // and its row-threshold words
+  hipStream_t ss[3];
+};
+
+int crp_plan(int m, int tau, int max_len, int64_t n_pairs, hipStream_t s, CrpPlan& P) {
+  const int L = stacked_len(max_len, m, tau);
+  if (L <= 0) {
+    set_error("max_len %d too short for m=%d tau=%d", max_len, m, tau);
+    return ACOSS_E_SHAPE;
+  }
+  P.m = m;
+  P.tau = tau;
+  P.L = L;
+  const int ld = P.ld = (int)align_up((size_t)L, 8);  // x16 B = 128 B: band rows never share a cache line
+  P.R = pick_R(m, ld);
+  if (P.R <= 0) {
+    set_error("track too long for the LDS stripe (stacked length %d)", ld);
+    return ACOSS_E_SHAPE;
+  }
+  P.sel_lds = select_lds_bytes(P.R, m, ld);
+  P.pan_lds = panel_lds_floats(32, m) * sizeof(float);
+  int rc;
+  if ((rc = set_lds(k_crp_select<false>, P.sel_lds))) return rc;
+  if ((rc = set_lds(k_crp_select<true>, P.sel_lds))) return rc;
+  if ((rc = set_lds(k_crp_panel<0>, P.pan_lds))) return rc;
+  if ((rc = set_lds(k_crp_panel<1>, P.pan_lds))) return rc;
+  P.nstrips = (L + 31) / 32;
+  P.thr_stride = ld;
+  P.mask_stride = (int64_t)P.nstrips * ld;
+  P.bnd_stride = (int64_t)((L + 2047) / 2048) * ld;
+  P.yrot_stride = (int64_t)align_up((size_t)max_len * 12, 64);
+  // split path (one sweep + two line-select kernels, crp_split.hip) needs 16-bit key planes;
+  // ACOSS_CRP_PATH=generic keeps a shape it covers on the generic kernels
+  static const char* path_env = getenv("ACOSS_CRP_PATH");
+  P.split = m == 9 && tau == 1 && L <= 4096 && !(path_env && strcmp(path_env, "generic") == 0);
+  // row pitch: the selects' 32-element runs end at align32(L); one pad column beyond them takes
+  // the sweep's branchless out-of-range stores
+  P.ldk = (int)align_up(align_up((size_t)L, 32) + 1, 64);
+  P.kstride = P.split ? (int64_t)align_up((size_t)L, 32) * P.ldk : 0;  // whole 32-row strips
+  // Two-level batching: a DP batch of nb_alloc pairs keeps its CRP words (0.5 MB per pair at
+  // 2000 frames) so the one-wave-per-pair DP launch is wide enough; the CRP itself runs in
+  // sub-batches whose 16-bit key planes (split path, 16 MB per pair) stay near the 256 MB
+  // Infinity Cache.
+  const size_t slot = 4 + 8 + 4 * (size_t)P.thr_stride * 4 + 4 * (size_t)P.mask_stride + 16 * (size_t)P.bnd_stride +
+                      4 * (size_t)P.yrot_stride;
+  size_t budget = (size_t)16 << 30;  // DP batch scratch: ~25k pairs at 2000 frames in one DP launch
+  if (const char* e = getenv("ACOSS_WS_BYTES")) budget = strtoull(e, nullptr, 10);
+  int64_t nbmax = (int64_t)(budget / slot);
+  if (const char* e = getenv("ACOSS_BATCH_PAIRS")) nbmax = atoll(e);
+  if (nbmax < 1) nbmax = 1;
+  if (nbmax > 65535) nbmax = 65535;
+  const int64_t nb_alloc = P.nb_alloc = n_pairs < nbmax ? n_pairs : nbmax;
+  P.sub = nb_alloc;
+  // split sub-batch scratch per pair: 16-bit prefixes row-major and strip-major (2 + 2 B per
+  // cell) and the row-threshold words RT
+  const size_t sub_pair = 4 * (size_t)P.kstride + 4 * (size_t)P.mask_stride;
+  if (P.split) {
+    size_t kbudget = (size_t)1 << 30;  // ~42 pairs at 2000 frames (x2 buffers): fills 256 CUs per launch
+    if (const char* e = getenv("ACOSS_KEY_BYTES")) kbudget = strtoull(e, nullptr, 10);
+    P.sub = (int64_t)(kbudget / sub_pair);
+    if (P.sub < 1) P.sub = 1;
+    if (P.sub > nb_alloc) P.sub = nb_alloc;
+  }
+  // split sub-batches alternate between the caller's stream and a side stream, each with its
+  // own key-plane buffer, so one sub-batch's selects overlap the next one's sweep
+  // read per call: bench.py takes its per-kernel profile with ACOSS_SPLIT_STREAMS=1, so the
+  // kernel durations of that call add up to its wall time
+  const char* e = getenv("ACOSS_SPLIT_STREAMS");
+  const int v = e ? atoi(e) : 2;
+  P.nbuf = !P.split ? 0 : (v < 1 ? 1 : (v > 3 ? 3 : v));
+  char* ws = static_cast<char*>(workspace(1, slot * nb_alloc + P.nbuf * sub_pair * P.sub + 8192));
+  if (!ws) return ACOSS_E_HIP;
+  size_t o = 0;
+  auto carve = [&](size_t bytes) {
+    void* r = ws + o;
+    o = align_up(o + bytes, 256);
+    return r;
+  };
+  P.oti = static_cast<int32_t*>(carve(4 * nb_alloc));
+  P.dims = static_cast<int2*>(carve(8 * nb_alloc));
+  P.thr_r = static_cast<float*>(carve(4 * P.thr_stride * nb_alloc));
+  P.T_r = static_cast<float*>(carve(4 * P.thr_stride * nb_alloc));
+  P.thr_c = static_cast<float*>(carve(4 * P.thr_stride * nb_alloc));
+  P.T_c = static_cast<float*>(carve(4 * P.thr_stride * nb_alloc));
+  P.mask = static_cast<uint32_t*>(carve(4 * P.mask_stride * nb_alloc));
+  P.bnd = static_cast<float4*>(carve(16 * P.bnd_stride * nb_alloc));
+  P.yrot = static_cast<float*>(carve(4 * P.yrot_stride * nb_alloc));
+  for (int b = 0; b < P.nbuf; ++b) {  // buffer 0 on the caller's stream, the others on side streams
+    P.kpl[b] = carve(4 * (size_t)P.kstride * P.sub);
+    P.rt[b] = static_cast<uint32_t*>(carve(4 * (size_t)P.mask_stride * P.sub));
+    P.ss[b] = b == 0 ? s : side_stream(b - 1);
+    if (b > 0 && !P.ss[b]) {
+      set_error("could not create the side stream");
+      return ACOSS_E_HIP;
+    }
+  }
+  return ACOSS_OK;
+}
+
+// Pairs [s0, ...) of the DP batch whose pairs start at pb, on C's tables.
+CrpBatch batch_view(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int s0) {
+  return CrpBatch{T.feats, T.X2, T.off, T.len, T.NX, T.ldn, pb + 2 * s0, C.oti + s0, C.dims + s0, C.m, C.tau,
+                  C.yrot + (size_t)s0 * C.yrot_stride, C.yrot_stride};
+}
+
+// One DP batch (nb <= C.nb_alloc pairs at pb) up to its CRP: OTI, rolled references, row and
+// column thresholds (thr_*, T_*) and the mask words, on stream s. The one place that chooses
+// between the split path and the generic kernels.
+int crp_masks(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int nb, const acoss_crp_params* params,
+              hipStream_t s) {
+  int rc;
+  prof_begin(PH_OTI, s);
+  hipLaunchKernelGGL(k_pair_oti, dim3((nb + 255) / 256), dim3(256), 0, s, T.prof, T.len, pb, (int64_t)nb, params->oti,
+                     C.m, C.tau, C.oti, C.dims);
+  ACOSS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_rotate_ref, dim3(16, nb), dim3(256), 0, s, T.feats, T.off, T.len, pb, C.oti, C.yrot,
+                     C.yrot_stride);
+  ACOSS_LAUNCH_CHECK();
+  prof_end(PH_OTI, s);
+  if (!C.split) {
+    const CrpBatch B = batch_view(C, T, pb, 0);
+    const dim3 sel_grid((C.L + C.R - 1) / C.R, nb);
+    prof_begin(PH_SEL_ROWS, s);
+    hipLaunchKernelGGL(k_crp_select<false>, sel_grid, dim3(256), C.sel_lds, s, B, C.R, C.ld, params->kappa,
+                       C.thr_r, C.T_r, C.thr_stride);
+    ACOSS_LAUNCH_CHECK();
+    prof_end(PH_SEL_ROWS, s);
+    prof_begin(PH_SEL_COLS, s);
+    hipLaunchKernelGGL(k_crp_select<true>, sel_grid, dim3(256), C.sel_lds, s, B, C.R, C.ld, params->kappa,
+                       C.thr_c, C.T_c, C.thr_stride);
+    ACOSS_LAUNCH_CHECK();
+    prof_end(PH_SEL_COLS, s);
+    prof_begin(PH_MASK, s);
+    hipLaunchKernelGGL(k_crp_panel<0>, dim3((C.L + kPanelW - 1) / kPanelW, C.nstrips, nb), dim3(256), C.pan_lds, s,
+                       B, C.T_r, C.T_c, C.thr_stride, C.mask, C.mask_stride, C.ld, (float*)nullptr);
+    ACOSS_LAUNCH_CHECK();
+    prof_end(PH_MASK, s);
+    return ACOSS_OK;
+  }
+  const int nsb = (int)((nb + C.sub - 1) / C.sub);  // sub-batches of this batch
+  const int nst = C.nbuf < nsb ? C.nbuf : nsb;      // streams they rotate over
+  if (nst > 1) {  // the side streams start after this batch's OTI / roll on the caller's stream
+    hipEvent_t e0 = sync_event(0);
+    ACOSS_HIP_CHECK(hipEventRecord(e0, s));
+    for (int q = 1; q < nst; ++q) ACOSS_HIP_CHECK(hipStreamWaitEvent(C.ss[q], e0, 0));
+  }
+  int k = 0;
+  for (int s0 = 0; s0 < nb; s0 += (int)C.sub, ++k) {
+    const int ns = (nb - s0) < C.sub ? (nb - s0) : (int)C.sub;
+    const int b = k % nst;
+    const size_t to = (size_t)s0 * C.thr_stride;
+    if ((rc = launch_crp_split(batch_view(C, T, pb, s0), ns, C.L, params->kappa, C.kpl[b], C.ldk, C.kstride, C.rt[b],
+                               C.thr_r + to, C.T_r + to, C.thr_c + to, C.T_c + to, C.thr_stride,
+                               C.mask + (size_t)s0 * C.mask_stride, C.mask_stride, C.ld, C.ss[b])))
+      return rc;
+  }
+  for (int q = 1; q < nst; ++q) {  // the caller's stream needs every sub-batch of every stream
+    hipEvent_t e1 = sync_event(q);
+    ACOSS_HIP_CHECK(hipEventRecord(e1, C.ss[q]));
+    ACOSS_HIP_CHECK(hipStreamWaitEvent(s, e1, 0));
   }
   return ACOSS_OK;
 }
@@ -1138,166 +1279,32 @@ extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, con
     return ACOSS_E_ARG;
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  const int m = params->m, tau = params->tau;
-  const int L = stacked_len(max_len, m, tau);
-  if (L <= 0) {
-    set_error("max_len %d too short for m=%d tau=%d", max_len, m, tau);
-    return ACOSS_E_SHAPE;
-  }
-  const int ld = (int)align_up((size_t)L, 8);  // x16 B = 128 B: band rows never share a cache line
-  Stage st;
-  if ((rc = prepare_stage(m, ld, &st))) return rc;
-  float *prof, *NX;
-  int ldn;
+  CrpPlan C;
+  if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, s, C))) return rc;
+  TrackPrep T;
   prof_begin(PH_PREP, s);
-  float* X2 = nullptr;
-  if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, m, tau, s, &prof, &NX, &ldn, &X2))) return rc;
+  if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, C.m, C.tau, s, &T))) return rc;
   prof_end(PH_PREP, s);
 
-  // per-pair slot: oti, dims, thr/T rows+cols, maskT, band boundary
-  const int nstrips = (L + 31) / 32;
-  const int nbands = (L + 2047) / 2048;
-  const int64_t thr_stride = ld;
-  const int64_t mask_stride = (int64_t)nstrips * ld;
-  const int64_t bnd_stride = (int64_t)nbands * ld;
-  const int64_t yrot_stride = (int64_t)align_up((size_t)max_len * 12, 64);
-  // split path (one sweep + two line-select kernels, crp_split.hip) needs 16-bit key planes
-  static const char* path_env = getenv("ACOSS_CRP_PATH");
-  const bool split = m == 9 && tau == 1 && L <= 4096 && !(path_env && strcmp(path_env, "fused") == 0);
-  // row pitch: the selects' 32-element runs end at align32(L); one pad column beyond them takes
-  // the sweep's branchless out-of-range stores
-  const int ldk = (int)align_up(align_up((size_t)L, 32) + 1, 64);
-  const int64_t kstride = split ? (int64_t)align_up((size_t)L, 32) * ldk : 0;  // whole 32-row strips
-  // Two-level batching: a DP batch of nb_alloc pairs keeps its CRP words (0.5 MB per pair at
-  // 2000 frames) so the one-wave-per-pair DP launch is wide enough; the CRP itself runs in
-  // sub-batches whose 16-bit key planes (split path, 16 MB per pair) stay near the 256 MB
-  // Infinity Cache.
-  const size_t slot = 4 + 8 + 4 * (size_t)thr_stride * 4 + 4 * (size_t)mask_stride + 16 * (size_t)bnd_stride +
-                      4 * (size_t)yrot_stride;
-  size_t budget = (size_t)16 << 30;  // DP batch scratch: ~25k pairs at 2000 frames in one DP launch
-  if (const char* e = getenv("ACOSS_WS_BYTES")) budget = strtoull(e, nullptr, 10);
-  int64_t nbmax = (int64_t)(budget / slot);
-  if (const char* e = getenv("ACOSS_BATCH_PAIRS")) nbmax = atoll(e);
-  if (nbmax < 1) nbmax = 1;
-  if (nbmax > 65535) nbmax = 65535;
-  const int64_t nb_alloc = n_pairs < nbmax ? n_pairs : nbmax;
-  int64_t sub = nb_alloc;
-  // split sub-batch scratch per pair: 16-bit prefixes row-major and strip-major (2 + 2 B per
-  // cell) and the row-threshold words RT
-  const size_t sub_pair = 4 * (size_t)kstride + 4 * (size_t)mask_stride;
-  if (split) {
-    size_t kbudget = (size_t)1 << 30;  // ~42 pairs at 2000 frames (x2 buffers): fills 256 CUs per launch
-    if (const char* e = getenv("ACOSS_KEY_BYTES")) kbudget = strtoull(e, nullptr, 10);
-    sub = (int64_t)(kbudget / sub_pair);
-    if (sub < 1) sub = 1;
-    if (sub > nb_alloc) sub = nb_alloc;
-  }
-  // split sub-batches alternate between the caller's stream and a side stream, each with its
-  // own key-plane buffer, so one sub-batch's selects overlap the next one's sweep
-  // read per call: bench.py takes its per-kernel profile with ACOSS_SPLIT_STREAMS=1, so the
-  // kernel durations of that call add up to its wall time
-  const int nbuf = [] {
-    const char* e = getenv("ACOSS_SPLIT_STREAMS");
-    const int v = e ? atoi(e) : 2;
-    return v < 1 ? 1 : (v > 3 ? 3 : v);
-  }();
-  const int nkb = nbuf;
-  char* ws = static_cast<char*>(workspace(1, slot * nb_alloc + (split ? nkb * sub_pair * sub : 0) + 8192));
-  if (!ws) return ACOSS_E_HIP;
-  size_t o = 0;
-  auto carve = [&](size_t bytes) {
-    char* r = ws + o;
-    o = align_up(o + bytes, 256);
-    return r;
-  };
-  int32_t* w_oti = reinterpret_cast<int32_t*>(carve(4 * nb_alloc));
-  int2* w_dims = reinterpret_cast<int2*>(carve(8 * nb_alloc));
-  float* w_thr_r = reinterpret_cast<float*>(carve(4 * thr_stride * nb_alloc));
-  float* w_T_r = reinterpret_cast<float*>(carve(4 * thr_stride * nb_alloc));
-  float* w_thr_c = reinterpret_cast<float*>(carve(4 * thr_stride * nb_alloc));
-  float* w_T_c = reinterpret_cast<float*>(carve(4 * thr_stride * nb_alloc));
-  uint32_t* w_mask = reinterpret_cast<uint32_t*>(carve(4 * mask_stride * nb_alloc));
-  float4* w_bnd = reinterpret_cast<float4*>(carve(16 * bnd_stride * nb_alloc));
-  float* w_yrot = reinterpret_cast<float*>(carve(4 * yrot_stride * nb_alloc));
-  void* w_kpl[3] = {nullptr, nullptr, nullptr};
-  uint32_t* w_rt[3] = {nullptr, nullptr, nullptr};
-  for (int b = 0; split && b < nkb; ++b) {
-    w_kpl[b] = static_cast<void*>(carve(4 * (size_t)kstride * sub));
-    w_rt[b] = reinterpret_cast<uint32_t*>(carve(4 * (size_t)mask_stride * sub));
-  }
-  hipStream_t ss[3] = {s, s, s};
-  for (int b = 1; split && b < nbuf; ++b) {
-    ss[b] = side_stream(b - 1);
-    if (!ss[b]) {
-      set_error("could not create the side stream");
-      return ACOSS_E_HIP;
-    }
-  }
-
   const bool eqg = params->gamma_open == params->gamma_ext;
-  for (int64_t base = 0; base < n_pairs; base += nb_alloc) {
-    const int nb = (int)((n_pairs - base) < nb_alloc ? (n_pairs - base) : nb_alloc);
-    const int32_t* pb = pairs + 2 * base;
-    prof_begin(PH_OTI, s);
-    hipLaunchKernelGGL(k_pair_oti, dim3((nb + 255) / 256), dim3(256), 0, s, prof, track_len, pb, (int64_t)nb,
-                       params->oti, m, tau, w_oti, w_dims);
-    ACOSS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_rotate_ref, dim3(16, nb), dim3(256), 0, s, feats, track_off, track_len, pb, w_oti, w_yrot,
-                       yrot_stride);
-    ACOSS_LAUNCH_CHECK();
-    prof_end(PH_OTI, s);
-    if (split) {
-      const int nsb = (int)((nb + sub - 1) / sub);     // sub-batches of this batch
-      const int nst = nbuf < nsb ? nbuf : nsb;         // streams they rotate over
-      if (nst > 1) {  // the side streams start after this batch's OTI / roll on the caller's stream
-        hipEvent_t e0 = sync_event(0);
-        ACOSS_HIP_CHECK(hipEventRecord(e0, s));
-        for (int q = 1; q < nst; ++q) ACOSS_HIP_CHECK(hipStreamWaitEvent(ss[q], e0, 0));
-      }
-      int k = 0;
-      for (int s0 = 0; s0 < nb; s0 += (int)sub, ++k) {
-        const int ns = (nb - s0) < sub ? (nb - s0) : (int)sub;
-        const int b = k % nst;
-        CrpBatch Bs{feats, X2, track_off, track_len, NX, ldn, pb + 2 * s0, w_oti + s0, w_dims + s0, m, tau,
-                    w_yrot + (size_t)s0 * yrot_stride, yrot_stride};
-        if ((rc = launch_crp_split(Bs, ns, L, params->kappa, w_kpl[b], ldk, kstride, w_rt[b],
-                                   w_thr_r + (size_t)s0 * thr_stride, w_T_r + (size_t)s0 * thr_stride,
-                                   w_thr_c + (size_t)s0 * thr_stride, w_T_c + (size_t)s0 * thr_stride, thr_stride,
-                                   w_mask + (size_t)s0 * mask_stride, mask_stride, ld, ss[b])))
-          return rc;
-      }
-      for (int q = 1; q < nst; ++q) {  // the DP (caller's stream) needs every sub-batch of every stream
-        hipEvent_t e1 = sync_event(q);
-        ACOSS_HIP_CHECK(hipEventRecord(e1, ss[q]));
-        ACOSS_HIP_CHECK(hipStreamWaitEvent(s, e1, 0));
-      }
-    } else {
-      CrpBatch B{feats, X2, track_off, track_len, NX, ldn, pb, w_oti, w_dims, m, tau, w_yrot, yrot_stride};
-      prof_begin(PH_SEL_ROWS, s);
-      if ((rc = run_select(false, st, B, nb, L, ld, params->kappa, w_thr_r, w_T_r, thr_stride, s))) return rc;
-      prof_end(PH_SEL_ROWS, s);
-      prof_begin(PH_SEL_COLS, s);
-      if ((rc = run_select(true, st, B, nb, L, ld, params->kappa, w_thr_c, w_T_c, thr_stride, s))) return rc;
-      prof_end(PH_SEL_COLS, s);
-      prof_begin(PH_MASK, s);
-      if ((rc = run_mask(st, B, nb, L, nstrips, w_T_r, w_T_c, thr_stride, w_mask, mask_stride, ld, s))) return rc;
-      prof_end(PH_MASK, s);
-    }
+  for (int64_t base = 0; base < n_pairs; base += C.nb_alloc) {
+    const int nb = (int)((n_pairs - base) < C.nb_alloc ? (n_pairs - base) : C.nb_alloc);
+    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
     if (qmax_out) {
       prof_begin(PH_DP_QMAX, s);
-      launch_dp<0>(eqg, nb, L, w_mask, mask_stride, ld, w_dims, params->gamma_open, params->gamma_ext, w_bnd,
-                   bnd_stride, qmax_out + base, s);
+      launch_dp<0>(eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
+                   C.bnd_stride, qmax_out + base, s);
       ACOSS_LAUNCH_CHECK();
       prof_end(PH_DP_QMAX, s);
     }
     if (dmax_out) {
       prof_begin(PH_DP_DMAX, s);
-      launch_dp<1>(eqg, nb, L, w_mask, mask_stride, ld, w_dims, params->gamma_open, params->gamma_ext, w_bnd,
-                   bnd_stride, dmax_out + base, s);
+      launch_dp<1>(eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
+                   C.bnd_stride, dmax_out + base, s);
       ACOSS_LAUNCH_CHECK();
       prof_end(PH_DP_DMAX, s);
     }
-    if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, w_oti, 4 * nb, hipMemcpyDeviceToDevice, s));
+    if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
   }
   return ACOSS_OK;
 }
@@ -1315,31 +1322,19 @@ extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t
     return ACOSS_E_SHAPE;
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  const int L = Mp > Np ? Mp : Np;
-  const int ld = (int)align_up((size_t)L, 8);  // x16 B = 128 B: band rows never share a cache line
-  Stage st;
-  if ((rc = prepare_stage(m, ld, &st))) return rc;
-  // packed features + tables in workspace slot 2
-  const int nstrips = (Mp + 31) / 32;
+  // the pair as a corpus of two tracks and a batch of one pair: packed features and the tables a
+  // caller of acoss_crp_align passes in, in workspace slot 2
+  const int max_len = M > N ? M : N;
+  CrpPlan C;
+  if ((rc = crp_plan(m, tau, max_len, 1, s, C))) return rc;
   const size_t fbytes = align_up((size_t)(M + N) * 12 * 4, 256);
-  const size_t ybytes = align_up((size_t)N * 12 * 4, 256);
-  const size_t bytes = fbytes + 256 * 4 + 4 * 4 * (size_t)ld + 4 * (size_t)nstrips * ld + ybytes;
-  char* ws = static_cast<char*>(workspace(2, bytes));
+  char* ws = static_cast<char*>(workspace(2, fbytes + 256));
   if (!ws) return ACOSS_E_HIP;
   float* f = reinterpret_cast<float*>(ws);
   char* tab = ws + fbytes;
   int64_t* d_off = reinterpret_cast<int64_t*>(tab);
   int32_t* d_len = reinterpret_cast<int32_t*>(tab + 64);
   int32_t* d_pairs = reinterpret_cast<int32_t*>(tab + 128);
-  int32_t* d_oti = reinterpret_cast<int32_t*>(tab + 192);
-  int2* d_dims = reinterpret_cast<int2*>(tab + 256);
-  float* thr_r = reinterpret_cast<float*>(tab + 1024);
-  float* T_r = thr_r + ld;
-  float* thr_c = T_r + ld;
-  float* T_c = thr_c + ld;
-  uint32_t* maskT = reinterpret_cast<uint32_t*>(T_c + ld);
-  float* yrot = reinterpret_cast<float*>(reinterpret_cast<char*>(maskT) + 4 * (size_t)nstrips * ld);
-  yrot = reinterpret_cast<float*>(align_up(reinterpret_cast<uintptr_t>(yrot), 256));
   const int64_t h_off[2] = {0, M};
   const int32_t h_len[2] = {M, N};
   const int32_t h_pairs[2] = {0, 1};
@@ -1349,30 +1344,21 @@ extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t
   ACOSS_HIP_CHECK(hipMemcpy(d_off, h_off, sizeof(h_off), hipMemcpyHostToDevice));
   ACOSS_HIP_CHECK(hipMemcpy(d_len, h_len, sizeof(h_len), hipMemcpyHostToDevice));
   ACOSS_HIP_CHECK(hipMemcpy(d_pairs, h_pairs, sizeof(h_pairs), hipMemcpyHostToDevice));
-  float *prof, *NX;
-  int ldn;
-  if ((rc = run_prep(f, d_off, d_len, 2, M > N ? M : N, m, tau, s, &prof, &NX, &ldn))) return rc;
-  hipLaunchKernelGGL(k_pair_oti, dim3(1), dim3(64), 0, s, prof, d_len, d_pairs, (int64_t)1, params->oti, m, tau,
-                     d_oti, d_dims);
-  ACOSS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_rotate_ref, dim3(16, 1), dim3(256), 0, s, f, d_off, d_len, d_pairs, d_oti, yrot, (int64_t)0);
-  ACOSS_LAUNCH_CHECK();
-  CrpBatch B{f, nullptr, d_off, d_len, NX, ldn, d_pairs, d_oti, d_dims, m, tau, yrot, 0};
-  if ((rc = run_select(false, st, B, 1, L, ld, params->kappa, thr_r, T_r, (int64_t)ld, s))) return rc;
-  if ((rc = run_select(true, st, B, 1, L, ld, params->kappa, thr_c, T_c, (int64_t)ld, s))) return rc;
+  TrackPrep T;
+  if ((rc = run_prep(f, d_off, d_len, 2, max_len, m, tau, s, &T))) return rc;
+  if ((rc = crp_masks(C, T, d_pairs, 1, params, s))) return rc;
   if (dist) {
-    hipLaunchKernelGGL(k_crp_panel<1>, dim3((Np + kPanelW - 1) / kPanelW, nstrips, 1), dim3(256), st.pan_lds, s, B,
-                       T_r, T_c, (int64_t)ld, maskT, (int64_t)0, ld, dist);
+    hipLaunchKernelGGL(k_crp_panel<1>, dim3((Np + kPanelW - 1) / kPanelW, C.nstrips, 1), dim3(256), C.pan_lds, s,
+                       batch_view(C, T, d_pairs, 0), C.T_r, C.T_c, C.thr_stride, C.mask, C.mask_stride, C.ld, dist);
     ACOSS_LAUNCH_CHECK();
   }
   if (crp) {
-    if ((rc = run_mask(st, B, 1, L, nstrips, T_r, T_c, (int64_t)ld, maskT, (int64_t)0, ld, s))) return rc;
-    hipLaunchKernelGGL(k_unpack_mask, dim3((Np + 255) / 256, Mp), dim3(256), 0, s, maskT, ld, Mp, Np, crp);
+    hipLaunchKernelGGL(k_unpack_mask, dim3((Np + 255) / 256, Mp), dim3(256), 0, s, C.mask, C.ld, Mp, Np, crp);
     ACOSS_LAUNCH_CHECK();
   }
-  if (thr_row) ACOSS_HIP_CHECK(hipMemcpyAsync(thr_row, thr_r, 4 * (size_t)Mp, hipMemcpyDeviceToDevice, s));
-  if (thr_col) ACOSS_HIP_CHECK(hipMemcpyAsync(thr_col, thr_c, 4 * (size_t)Np, hipMemcpyDeviceToDevice, s));
-  if (oti) ACOSS_HIP_CHECK(hipMemcpyAsync(oti, d_oti, 4, hipMemcpyDeviceToDevice, s));
+  if (thr_row) ACOSS_HIP_CHECK(hipMemcpyAsync(thr_row, C.thr_r, 4 * (size_t)Mp, hipMemcpyDeviceToDevice, s));
+  if (thr_col) ACOSS_HIP_CHECK(hipMemcpyAsync(thr_col, C.thr_c, 4 * (size_t)Np, hipMemcpyDeviceToDevice, s));
+  if (oti) ACOSS_HIP_CHECK(hipMemcpyAsync(oti, C.oti, 4, hipMemcpyDeviceToDevice, s));
   ACOSS_HIP_CHECK(hipStreamSynchronize(s));
   return ACOSS_OK;
 }

@@ -1,4 +1,4 @@
-// crp_internal.hpp — types shared by the Serra09/Chen kernels (crp.hip, crp_select.hip).
+// crp_internal.hpp — types shared by the Serra09/Chen kernels (crp.hip, crp_split.hip).
 #pragma once
 #include "common.hpp"
 
@@ -25,20 +25,13 @@ struct CrpBatch {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(4))) const f32x4 cfloat4;
 
-// Fast threshold kernels (crp_select.hip). Returns ACOSS_OK, an error code, or 1 when the
-// shape is not covered by the fast path (caller falls back to k_crp_select).
-// Fast CRP mask kernel (crp_mask.hip); 1 = not covered (caller falls back to k_crp_panel<0>).
-int launch_mask9(const CrpBatch& B, int nb, int L, const float* Trow, const float* Tcol, int64_t thr_stride,
-                 uint32_t* maskT, int64_t mask_stride, int ld, hipStream_t s);
-
-// Two-kernel CRP around one sweep (crp_split.hip); 1 = not covered.
+// Two-kernel CRP around one sweep (crp_split.hip): thresholds and mask words of nb pairs with
+// m = 9, tau = 1 and lines of at most L <= 4096 codes; 1 = not covered (crp.hip's crp_masks
+// decides by the same rule and runs the generic k_crp_select / k_crp_panel instead).
 // kplanes: 2 planes of nb*kstride uint16 (16-bit key prefixes, row-major and strip-major).
 int launch_crp_split(const CrpBatch& B, int nb, int L, float kappa, void* kplanes, int ldk,
                      int64_t kstride,
                      uint32_t* RT, float* thr_r, float* T_r, float* thr_c, float* T_c, int64_t thr_stride,
                      uint32_t* maskT, int64_t mask_stride, int ld, hipStream_t s);
-
-int launch_select16(bool trans, const CrpBatch& B, int nb, int L, float kappa, float* thr, float* T,
-                    int64_t thr_stride, hipStream_t s);
 
 }  // namespace acoss

@@ -75,7 +75,9 @@ int acoss_crp_align(const float* feats, const int64_t* track_off, const int32_t*
  * X: (M x 12), Y: (N x 12) device float32. Outputs (device, each may be NULL):
  *   dist (Mp x Np) float32 stacked Euclidean distances, thr_row (Mp), thr_col (Np) float32
  *   percentile thresholds, crp (Mp x Np) uint8 mutual-neighbour mask, oti (1) int32.
- * Mp = ceil((M - m*tau)/tau), Np likewise (essentia stackChromaFrames). */
+ * Mp = ceil((M - m*tau)/tau), Np likewise (essentia stackChromaFrames).
+ * thr_row, thr_col and crp come from the kernels acoss_crp_align runs for this shape, as a batch
+ * of one pair; dist from the generic panel kernel. */
 int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params* params,
                    float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti, void* hip_stream);
 

@@ -20,8 +20,13 @@ def _pair(rng, M, N):
     return X, Y
 
 
+# m = 9, tau = 1: the split kernels (crp_split.hip), one case per line type of their selects:
+# LineS<8> (lines <= 512 codes), LineS<16> (513..1024), the long-line type (1025..2048); Line2
+# (2049..4096) is in test_crp_pair_degenerate_rows. (41, 42): lines of exactly 32 and 33 codes,
+# the run edge the key planes' kNone padding must cover. The other two pin the generic kernels.
 @pytest.mark.parametrize("M,N,m,tau,oti", [(60, 70, 9, 1, True), (300, 257, 9, 1, True), (523, 611, 9, 2, True),
-                                            (200, 180, 4, 1, False), (2000, 2000, 9, 1, True)])
+                                            (200, 180, 4, 1, False), (2000, 2000, 9, 1, True),
+                                            (700, 1000, 9, 1, True), (41, 42, 9, 1, True)])
 def test_crp_pair_intermediates_bitexact(M, N, m, tau, oti):
     rng = np.random.Generator(np.random.PCG64(M * 1000 + N))
     X, Y = _pair(rng, M, N)
@@ -90,15 +95,16 @@ def test_crp_pair_degenerate_rows(M, N, silence):
 
 
 @pytest.mark.parametrize("path", [
-    "split", "fused",
+    "split", "generic",
     # the alternative kernels the runtime switches select (read once per process, hence the
-    # subprocess): generic LDS-Gram select and mask on the fused path, the one-pair-per-wave and
-    # the general DP, the f32 chen17 DP instead of the packed one, no lane-strided short lines
-    "fused:ACOSS_SELECT_GENERIC=1:ACOSS_MASK_GENERIC=1",
+    # subprocess): the one-pair-per-wave and the general DP, the f32 chen17 DP instead of the
+    # packed one, no lane-strided short lines
     "split:ACOSS_DP_NOGROUP=1", "split:ACOSS_DP_NOFAST=1", "split:ACOSS_DP_F32=1", "split:ACOSS_NO_SHORT=1"])
 def test_crp_align_degenerate_batch(path, monkeypatch):
     """Batch path on silences / ragged lengths / long tracks, both CRP implementations and every
-    alternative kernel behind a runtime switch: each equal to the oracle."""
+    alternative kernel behind a runtime switch: each equal to the oracle. Then the single-pair
+    entry point under the same switch: its thresholds and mask are the intermediates of the
+    kernels the batch has just run."""
     import subprocess
     import sys
     import os
@@ -122,6 +128,12 @@ got = _lib.crp_align(feats, off, lens, int(lens.max()), pairs, _lib.crp_params()
 assert np.array_equal(got["oti"].cpu().numpy(), k)
 assert np.array_equal(got["qmax"].cpu().numpy(), q), (got["qmax"].cpu().numpy(), q)
 assert np.array_equal(got["dmax"].cpu().numpy(), d)
+X, Y = tracks[1], tracks[3]
+ref = oracle.crp_pair(X, Y)
+one = _lib.crp_pair(X, Y, _lib.crp_params(), dist=False)
+for key in ("thr_row", "thr_col"):
+    assert np.array_equal(one[key].cpu().numpy().view(np.uint32), ref[key].view(np.uint32)), key
+assert np.array_equal(one["crp"].cpu().numpy(), ref["crp"])
 print("ok")
 ''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
        os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "acoss-1_amd"))
@@ -198,7 +210,7 @@ def test_crp_align_long_lines():
 
 def test_crp_align_past_split_limit():
     """A launch with a line of 4097 codes (a 4106-frame track) leaves the split path for the
-    generic fused kernels; results stay bit-exact."""
+    generic kernels; results stay bit-exact."""
     rng = np.random.Generator(np.random.PCG64(13))
     tracks = [synthetic.render(rng, synthetic.base_sequence(rng, n)) for n in (300, 4106)]
     feats, off, lens = synthetic.pack(tracks)
