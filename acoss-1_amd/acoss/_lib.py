@@ -66,6 +66,9 @@ SIGNATURES = {
                           _i32, _f32, _vp, _vp],
     "acoss_ef_block_features": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                 _vp, _vp],
+    "acoss_ftm2d_shingles": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, ctypes.c_double, ctypes.c_double, _vp, _vp],
+    "acoss_ftm2d_beatsync": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.c_double, _vp, _vp, _vp],
+    "acoss_ftm2d_scores": [_vp, _i32, _i32, _vp, _i64, _vp, _vp],
     "acoss_ds_finish": [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp],
     "acoss_eval_ranks": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "acoss_release_workspace": [],
@@ -721,6 +724,109 @@ def ef_block_features(chromas, mfccs, onsets, blocksize=20, mfccs_per_block=50, 
     _check(rc, "acoss_ef_block_features")
     out["block_off"] = boff
     out["n_blocks"] = nb.astype(np.int32)
+    return out
+
+
+FTM2D_MAX_WINDOWS = 4096  # windows per track (ftm2d.hip sorts them in LDS), as SiMPle caps frames
+
+
+def ftm2d_bounds(chromas, onsets, win=75):
+    """Host half of ftm2d_shingles (no GPU): pack the tracks and build every track's segment
+    boundaries, np.unique(concat([0], clip(onsets, 0, n), [n])) (what librosa.util.sync slices at,
+    ftm2d.py:58). Raises ValueError naming every track with fewer than `win` beats (the reference's
+    btchroma_to_fftmat returns None there and crashes, :129-130) or more than win - 1 + 4096.
+    Returns (feats (sum n, 12) f32, off i64, lens i32, bounds i64, bound_off i64 (T + 1))."""
+    from .synthetic import pack
+    T = len(chromas)
+    if len(onsets) != T:
+        raise ValueError("one chroma and one onset array per track")
+    tracks = [np.asarray(c, np.float32) for c in chromas]
+    for t, c in enumerate(tracks):
+        if c.ndim != 2 or c.shape[1] != 12:
+            raise ValueError("track %d: chroma must be (n_frames, 12)" % t)
+    bnds, bad = [], []
+    for t, (c, o) in enumerate(zip(tracks, onsets)):
+        n = len(c)
+        o = np.clip(np.asarray(o, np.int64).ravel(), 0, n)
+        b = np.unique(np.concatenate([np.zeros(1, np.int64), o, np.full(1, n, np.int64)]))
+        nb = len(b) - 1
+        if nb < win:
+            bad.append("track %d: %d beats, fewer than WIN=%d" % (t, nb, win))
+        elif nb > win - 1 + FTM2D_MAX_WINDOWS:
+            bad.append("track %d: %d beats, more than %d (%d windows)" % (t, nb, win - 1 + FTM2D_MAX_WINDOWS,
+                                                                        FTM2D_MAX_WINDOWS))
+        bnds.append(b)
+    if bad:
+        raise ValueError("FTM2D: " + "; ".join(bad))
+    bound_off = np.zeros(T + 1, np.int64)
+    bound_off[1:] = np.cumsum([len(b) for b in bnds])
+    bounds = np.concatenate(bnds) if T else np.zeros(0, np.int64)
+    feats, off, lens = pack(tracks)
+    return feats, off, lens, bounds.astype(np.int64), bound_off
+
+
+def ftm2d_shingles(chromas, onsets, win=75, pwr=1.96, C=5):
+    """FTM2D.load_features for every track (ftm2d.py:52-66): chromas, a list of (n_t, 12) arrays,
+    and onsets, a list of frame-index arrays -> (N, 12 * win) float64 device tensor of shingles."""
+    packed = ftm2d_bounds(chromas, onsets, win)  # raises before any launch
+    torch = _torch()
+    lib = load_library()
+    feats, off, lens, bounds, bound_off = packed
+    T = len(lens)
+    out = torch.empty((T, 12 * int(win)), dtype=torch.float64, device="cuda")
+    if T == 0:
+        return out
+    # keep every device buffer referenced until the launch is queued
+    f = _dev(feats, torch.float32)
+    o = _dev(off, torch.int64)
+    ln = _dev(lens, torch.int32)
+    b = _dev(bounds, torch.int64)
+    bo = _dev(bound_off, torch.int64)
+    rc = lib.acoss_ftm2d_shingles(_ptr(f), _ptr(o), _ptr(ln), T, int(lens.max(initial=0)), _ptr(b), _ptr(bo), int(win),
+                                  float(pwr), float(C), _ptr(out), _stream())
+    _check(rc, "acoss_ftm2d_shingles")
+    return out
+
+
+def ftm2d_beatsync(chromas, onsets, pwr=1.96):
+    """The first two steps of ftm2d_shingles alone (parity tests): per track the (12, beats)
+    float32 beat-synchronous medians and their float64 chrompwr, as lists of numpy arrays."""
+    packed = ftm2d_bounds(chromas, onsets, win=0)
+    torch = _torch()
+    lib = load_library()
+    feats, off, lens, bounds, bound_off = packed
+    T = len(lens)
+    nb = np.diff(bound_off) - 1
+    cols = int(nb.sum())
+    sync = torch.empty(max(1, 12 * cols), dtype=torch.float32, device="cuda")
+    chroma = torch.empty(max(1, 12 * cols), dtype=torch.float64, device="cuda")
+    f = _dev(feats, torch.float32)
+    o = _dev(off, torch.int64)
+    ln = _dev(lens, torch.int32)
+    b = _dev(bounds, torch.int64)
+    bo = _dev(bound_off, torch.int64)
+    rc = lib.acoss_ftm2d_beatsync(_ptr(f), _ptr(o), _ptr(ln), T, _ptr(b), _ptr(bo), int(nb.max(initial=0)), float(pwr),
+                                  _ptr(sync), _ptr(chroma), _stream())
+    _check(rc, "acoss_ftm2d_beatsync")
+    sh, ch = sync.cpu().numpy(), chroma.cpu().numpy()
+    col0 = bound_off[:-1] - np.arange(T)
+    return ([sh[12 * c:12 * (c + n)].reshape(12, n) for c, n in zip(col0, nb)],
+            [ch[12 * c:12 * (c + n)].reshape(12, n) for c, n in zip(col0, nb)])
+
+
+def ftm2d_scores(shingles, pairs):
+    """FTM2D.similarity (ftm2d.py:85-97): exp(-|s_i - s_j|^2) of the (P, 2) pairs -> (P,) float64
+    device tensor. shingles: (N, dim) float64."""
+    torch = _torch()
+    lib = load_library()
+    S = _dev(shingles, torch.float64)
+    if S.dim() != 2:
+        raise ValueError("shingles must be (N, dim)")
+    pairs, _ = _pairs_dev(pairs, int(S.shape[0]))
+    P = int(pairs.shape[0])
+    out = torch.empty(P, dtype=torch.float64, device="cuda")
+    rc = lib.acoss_ftm2d_scores(_ptr(S), int(S.shape[0]), int(S.shape[1]), _ptr(pairs), P, _ptr(out), _stream())
+    _check(rc, "acoss_ftm2d_scores")
     return out
 
 

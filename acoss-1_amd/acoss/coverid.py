@@ -4,7 +4,8 @@ Same dispatch and call sequence per algorithm as the reference (coverid.py:22-14
 reference defects are not reproduced: "EarlyFusionTraile" dispatches
 (the reference only matches "EarlyFusion", :72), and `parallel` does not crash (the pairs
 are batched on the GPU; with torch.distributed initialised every rank takes a stripe).
-FTM2D is outside this engine's scope and raises NotImplementedError.
+All five names of `algorithm_names` run on the engine; FTM2D (coverid.py:107-122) makes its
+shingles in `prepare()` and scores the pairs symmetrically.
 """
 import argparse
 import sys
@@ -63,8 +64,14 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         logger.info('Feature loading done...')
         logger.info('Computing pairwise similarity...')
         algo.all_pairwise(parallel, n_cores=n_workers, symmetric=False)
-    else:
-        raise NotImplementedError("FTM2D is outside the scope of the MI355X engine (DESIGN.md)")
+    else:  # "FTM2D" (coverid.py:107-122)
+        from .algorithms.ftm2d import FTM2D
+        algo = FTM2D(**kw)
+        # the reference's load_features(i) loop (:114-115): every shingle in one launch
+        algo.prepare()
+        logger.info('Feature loading done...')
+        logger.info('Computing pairwise similarity...')
+        algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True)
     logger.info('Running benchmark evaluations on the given dataset - %s' % dataset_csv)
     for similarity_type in list(algo.Ds.keys()):
         algo.getEvalStatistics(similarity_type)

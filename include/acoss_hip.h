@@ -188,6 +188,41 @@ int acoss_simple_features(const float* feats, const int64_t* track_off, const in
                           int32_t win, int32_t skip, const double* smooth, int32_t smooth_len, double* out,
                           const int64_t* out_off, int64_t out_elems, void* hip_stream);
 
+/* FTM2D shingles (FTM2D.load_features, acoss/algorithms/ftm2d.py:52-66, with chrompwr :100-117 and
+ * btchroma_to_fftmat :120-138) for a batch of tracks. feats: packed (sum n, 12) float32 chroma as
+ * above; max_len = max n. bounds: every track's segment boundaries, int64 frame indices, sorted,
+ * unique and clipped to [0, n_t] (np.unique(concat([0], clip(onsets, 0, n), [n])), what
+ * librosa.util.sync(hpcp.T, onsets) slices at, :58); track t's are bounds[bound_off[t] ..
+ * bound_off[t + 1]), bound_off int64[n_tracks + 1] with bound_off[0] = 0, so the track has
+ * bound_off[t + 1] - bound_off[t] - 1 beats. Per track: the float32 median of every (segment, bin)
+ * exactly as np.median, chrompwr(., pwr), |fft2| of every 12 x win window fftshift-ed and flattened
+ * row-major, each window divided by its L2 norm (0 -> 1) and mapped by log(C x + 1), the
+ * per-coefficient median over the windows, divided by the L2 norm of the medians (NaN for an
+ * all-silent track, as the reference's 0 / 0); float64 from chrompwr on.
+ * shingles_out: (n_tracks x 12 win) float64. win must be 75 (ACOSS_E_ARG otherwise): the twiddle
+ * matrix' size is a compile-time constant. A track with fewer than win beats or more than 4170
+ * (4096 windows) returns ACOSS_E_SHAPE, the message naming the track index; the offsets are read
+ * back from the device for that check, which synchronises the stream once. */
+int acoss_ftm2d_shingles(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                         int32_t max_len, const int64_t* bounds, const int64_t* bound_off, int32_t win, double pwr,
+                         double C, double* shingles_out, void* hip_stream);
+
+/* The first two steps of acoss_ftm2d_shingles alone, for parity tests (ftm2d.py:58-59, 100-117):
+ * track t's beat-synchronous medians (sync_out, float32, may be NULL) and their chrompwr (chroma_out,
+ * float64) as (12 x beats) blocks at element offset 12 (bound_off[t] - t). max_beats = the largest
+ * beat count (host scalar); any segment length is accepted. */
+int acoss_ftm2d_beatsync(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                         const int64_t* bounds, const int64_t* bound_off, int32_t max_beats, double pwr,
+                         float* sync_out, double* chroma_out, void* hip_stream);
+
+/* FTM2D pair scores (FTM2D.similarity, ftm2d.py:85-97): scores_out[p] = exp(-sum_d (s_i[d] - s_j[d])^2)
+ * for (i, j) = (pairs[2p], pairs[2p+1]), float64, the squared differences summed directly in one
+ * fixed order (a pair's score does not depend on its place in the list; (i, i) scores exactly 1).
+ * shingles: (n_tracks x dim) float64, dim <= 1024 (900 for acoss_ftm2d_shingles' output). A pair
+ * naming a track outside [0, n_tracks) scores NaN. */
+int acoss_ftm2d_scores(const double* shingles, int32_t n_tracks, int32_t dim, const int32_t* pairs, int64_t n_pairs,
+                       double* scores_out, void* hip_stream);
+
 /* Batched EarlyFusion scores (A15: EarlyFusion.similarity, acoss/algorithms/earlyfusion_traile.py:157-198).
  * Block features of every track packed row-major: mfcc (sum nb x d_mfcc), ssm (sum nb x d_ssm),
  * chroma (sum nb x d_chroma, 12-bin blocks) float32, track t's rows at block_off[t], n_blocks[t]
