@@ -54,6 +54,8 @@ def lib():
                                    ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_float, _fp, _fp, _i32p,
                                    ctypes.c_int]
         L.or_crp_dist.argtypes = [_fp, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp]
+        L.or_crp_thresholds.restype = None
+        L.or_crp_thresholds.argtypes = [_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, _fp, _fp]
         L.or_sw_constrained.restype = ctypes.c_double
         L.or_sw_constrained.argtypes = [_u8p, ctypes.c_int, ctypes.c_int]
         L.or_simple_sim.restype = ctypes.c_double
@@ -123,6 +125,16 @@ def crp_dist(X, Y, k=0, m=9, tau=1):
     D = np.zeros((Mp, Np), np.float32)
     lib().or_crp_dist(_p(X, _fp), len(X), _p(Y, _fp), len(Y), int(k), m, tau, _p(D, _fp))
     return D
+
+
+def crp_thresholds(D, kappa=0.095):
+    """Percentile thresholds of every row and column of a distance matrix -> (thr_row, thr_col)."""
+    D = np.ascontiguousarray(D, np.float32)
+    Mp, Np = D.shape
+    tr = np.zeros(Mp, np.float32)
+    tc = np.zeros(Np, np.float32)
+    lib().or_crp_thresholds(_p(D, _fp), Mp, Np, kappa, _p(tr, _fp), _p(tc, _fp))
+    return tr, tc
 
 
 def crp_batch(feats, off, lens, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5,
