@@ -4,11 +4,13 @@
 // latefusion_chen.py:63-69): stacked distances, percentile(row/column, 9.5) and the mutual
 // binary mask, bit-identical to oracle/crp_oracle.cpp.
 //
-//  k_sweep_rows9  one 256-thread block per (32-row strip, pair). Systolic walk (no LDS): lane =
+//  k_sweep_rows9  one 256-thread block per (32-row strip, pair). Systolic walk in registers: lane =
 //                 reference column, query frames as SGPR pairs, 9-term diagonal windows carried
 //                 one lane per step by DPP; every squared-distance key leaves as its HIGH 16
 //                 bits only, twice: row-major Hr[i][j] and strip-major Hc[i/32][j][32 rows in
-//                 split word order]. Then the fused row select: one wave per CRP row on Hr, the
+//                 split word order], both through a per-wave LDS tile that turns a block's
+//                 prefixes into 16-byte pieces of the plane.
+//                 Then the fused row select: one wave per CRP row on Hr, the
 //                 16-bit prefixes of the two order statistics by a hinted SWAR-count search (7-bit
 //                 window codes around the hint), the tied prefix group's exact keys RECOMPUTED
 //                 (cell_key, one batched round, ~20-30 cells) and ranked -> percentile ->
@@ -131,16 +133,11 @@ struct LineCells {
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-// Global-address-space u16 pointer: a pointer pinned to SGPRs by an empty asm loses its address
-// space, and generic (flat) stores count in lgkmcnt too, so every s_waitcnt for the LDS reads
-// would also wait for the previous rows' stores to be acknowledged.
+// Global-address-space u16 pointer for the key planes' stores: generic (flat) stores count in
+// lgkmcnt too, so every s_waitcnt for an LDS read would also wait for the previous stores to be
+// acknowledged. The stores take a 32-bit byte offset from an SGPR base (saddr form; an element
+// index would need a 64-bit address per store).
 typedef __attribute__((address_space(1))) uint16_t gu16;
-// Store at a 32-bit byte offset from an SGPR base: global_store_short v_off, v, s[base] (saddr
-// form; a u16 element index would need a 64-bit address per store).
-__device__ __forceinline__ void st_u16(gu16* base, unsigned idx, unsigned v) {
-  typedef __attribute__((address_space(1))) char gchar;
-  *(gu16*)((gchar*)base + idx * 2u) = (uint16_t)v;
-}
 
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 
@@ -153,28 +150,33 @@ __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __bu
 // lane c - jb at step r and moves one lane per step (v_add_f32 with a DPP wave_shr:1 operand),
 // collecting G(r + u, c + u) in the canonical sequential order; it completes on lane
 // c - jb + 8 at step r + 8. Lanes 0..7 finish windows that began left of the block and are
-// dropped: kSysCols = 56 valid columns per 64 lanes. No LDS and no barriers: each lane owns
-// its output column's 32 rows, so the strip-major prefixes leave straight from registers (split
-// word order) and a step's row-major prefixes are 56 consecutive columns.
+// dropped: kSysCols = 56 valid columns per 64 lanes. No LDS and no barriers inside the walk:
+// each lane keeps its output column's 32 prefixes in 16 registers (split word order); after the
+// 40 steps both planes' pieces are formed in the wave's LDS tile (below).
 // ---------------------------------------------------------------------------------------
 constexpr int kSysCols = 56;
 constexpr int kThreads = 256;  // sweep block: 4 waves
+// Staging tile of one wave for the key planes' emit: a column block's 32 rows x 56 columns of
+// prefixes, read back as 16-byte pieces (row-major: 7 per row; strip-major: 4 per column)
+constexpr int kTileBytes = kSR * kSysCols * 2;  // 3,584
+constexpr int kTilePieces = kTileBytes / 16;    // 224
 
 __device__ __forceinline__ float dpp_shr1(float v) {  // lane l <- lane l - 1 (lane 0 <- 0)
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
 }
 
-// PARTIAL: the last strip of a pair (fewer than 32 rows in the track); the full strips keep a
-// branch-free emit.
+// PARTIAL: the last strip of a pair (fewer than 32 rows in the track); the full strips' emit
+// has no row tests.
 template <bool PARTIAL>
 __device__ __forceinline__ void sweep_body_sys(const PairView& V, int p, int strip, const KeyPlanes& K, int ldr,
-                                               int ldc, int64_t kstride, uint16_t* Hr) {
+                                               int ldc, int64_t kstride, uint16_t* Hr, char* smem) {
   constexpr int kSteps = kSR + kMS - 1;  // 40
   const int i0 = strip * kSR;
   const int rows = PARTIAL ? min(kSR, V.Mp - i0) : kSR;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint16_t* Hc = K.hc + (size_t)p * kstride;
+  uint16_t* tile = reinterpret_cast<uint16_t*>(smem + w * kTileBytes);  // this wave's staging tile
   const float* X2b = V.X2 + (size_t)i0 * 24;
   const float* Nq0 = V.NXq + i0;
   auto nqr = [&](int r) {  // row norm: a scalar load at a compile-time offset
@@ -215,12 +217,10 @@ __device__ __forceinline__ void sweep_body_sys(const PairView& V, int p, int str
       y[4 * q + 3] = ynext[q].w;
     }
     if (cb + 4 < nblk) load_y(jb + 4 * kSysCols, ynext);
-    // this lane's output column; dropped lanes and columns past N' store to the pad column
+    // this lane's output column (lanes 0..7 finish windows that began left of the block)
     const int col = jb + lane - (kMS - 1);
     const bool valid = lane >= kMS - 1 && col < V.Np;
-    const unsigned hcol = valid ? (unsigned)col : (unsigned)(ldr - 1);
     const float ny = valid ? V.NXr[col] : 0.0f;
-    gu16* hrow = (gu16*)Hr;
     float A[kMS];  // A[u]: window of row kk - u after u + 1 terms
     unsigned kh[16];    // rows 0..15: full keys until their split partner (row + 16) is done
     unsigned hw[16];    // split-order words: rows (h, h + 16)
@@ -251,16 +251,10 @@ __device__ __forceinline__ void sweep_body_sys(const PairView& V, int p, int str
         const f32x2 d2 = pk_fma(f32x2{-2.0f, -2.0f}, f32x2{dots[0], dots[1]}, nq) + f32x2{ny, ny};
         unsigned k0 = __builtin_bit_cast(unsigned, d2.x > 0.0f ? d2.x : 0.0f);
         unsigned k1 = __builtin_bit_cast(unsigned, d2.y > 0.0f ? d2.y : 0.0f);
-        if (!PARTIAL || r + 1 < rows) {  // wave-uniform; rows past M' are never stored
-          st_u16(hrow, hcol, k0 >> 16);
-          st_u16(hrow, (unsigned)ldr + hcol, k1 >> 16);
-        } else {
-          if (r < rows) st_u16(hrow, hcol, k0 >> 16);
-          if (r >= rows) k0 = kNone << 16;  // and read as "no element" in the column plane
-          k1 = kNone << 16;
+        if (PARTIAL) {  // wave-uniform; rows past M' read as "no element" in the column plane
+          if (r >= rows) k0 = kNone << 16;
+          if (r + 1 >= rows) k1 = kNone << 16;
         }
-        hrow += 2 * ldr;
-        asm volatile("" : "+s"(hrow));
         if (r < 16) {
           kh[r] = k0;
           kh[r + 1] = k1;
@@ -270,43 +264,81 @@ __device__ __forceinline__ void sweep_body_sys(const PairView& V, int p, int str
         }
       }
     }
-    // strip-major stores in 64-byte runs: a 4 x 4 transpose of the 16-byte pieces inside each lane
-    // quad (two DPP butterfly stages per piece word), then store k: lane b + m (b = lane & ~3)
-    // writes piece m of lane b + k's column, so a quad writes one column's 64 bytes contiguously
-    // (each lane writing its own column's four pieces at a 64-byte stride: ACOSS_HC_LANE_STORES,
-    // 1.5 % slower at 2,000 frames, profiles/r04/ab_hcquad2000.txt)
-    {
-      const int m = lane & 3, b = lane & ~3;
-      const bool o1 = (m & 1) != 0, o2 = (m & 2) != 0;
-      uint32_t T[4][4];
+    // Both planes leave through the wave's tile, 16 bytes per lane and store, from the split-order
+    // words (no LDS operation inside the step chain, whose scalar loads share lgkmcnt with it;
+    // writing the tile inside the chain measured the same, profiles/r07/README.txt).
+    // A wave's DS operations complete in order, so the wave barriers (no block barrier: the tile
+    // is wave-private) only pin the compiler's order.
+    typedef __attribute__((address_space(1))) char gchar;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) u32x4 gu4;
+    u32x4* tq = reinterpret_cast<u32x4*>(tile);
+    const int cc = lane - (kMS - 1);  // this lane's tile column
+    if (jb + kSysCols > V.Np) {  // wave-uniform, the pair's last column block: columns past N' as kNone
 #pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const uint32_t x0 = hw[d], x1 = hw[4 + d], x2 = hw[8 + d], x3 = hw[12 + d];
-        // every DPP on all lanes (left to itself the compiler sinks them under the selects' exec
-        // masks, where the partner lane is off and reads as 0)
-        uint32_t p0 = dpp_u32<0xB1>(x0, x0), p1 = dpp_u32<0xB1>(x1, x1), p2 = dpp_u32<0xB1>(x2, x2),
-                 p3 = dpp_u32<0xB1>(x3, x3);
-        asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3));
-        const uint32_t y0 = o1 ? p1 : x0, y1 = o1 ? x1 : p0, y2 = o1 ? p3 : x2, y3 = o1 ? x3 : p2;
-        uint32_t q0 = dpp_u32<0x4E>(y0, y0), q1 = dpp_u32<0x4E>(y1, y1), q2 = dpp_u32<0x4E>(y2, y2),
-                 q3 = dpp_u32<0x4E>(y3, y3);
-        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3));
-        T[0][d] = o2 ? q2 : y0;
-        T[1][d] = o2 ? q3 : y1;
-        T[2][d] = o2 ? y2 : q0;
-        T[3][d] = o2 ? y3 : q1;
-      }
+      for (int h = 0; h < 16; ++h) hw[h] = col < V.Np ? hw[h] : kNone * 0x10001u;
+    }
+    // row-major: lane l >= 8 writes its column's 32 prefixes to tile[r][l - 8]. A tile row is
+    // 112 B = 7 pieces of 16 B, so piece t (row t / 7, columns jb + 8 (t % 7) ..+7) sits at byte
+    // 16 t; lane l takes pieces l, l + 64, l + 128, l + 192 (< 224).
+    if (cc >= 0) {
+      uint16_t* tc = tile + cc;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int c = jb + b + k - (kMS - 1);
-        if (b + k >= kMS - 1 && c < V.Np)
-          reinterpret_cast<uint4*>(Hc + ((size_t)strip * ldc + c) * kSR)[m] = make_uint4(T[k][0], T[k][1], T[k][2], T[k][3]);
+      for (int h = 0; h < 16; ++h) {
+        tc[h * kSysCols] = (uint16_t)hw[h];
+        tc[(h + 16) * kSysCols] = (uint16_t)(hw[h] >> 16);
       }
+    }
+    __builtin_amdgcn_wave_barrier();
+    u32x4 pr[4], pq[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pr[k] = tq[min(lane + 64 * k, kTilePieces - 1)];
+    // every read in flight before the first store (left to itself the compiler sinks each under
+    // its store's exec mask: serial LDS round trips)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(pr[k].x), "+v"(pr[k].y), "+v"(pr[k].z), "+v"(pr[k].w));
+    // jb = 56 cb and the row pitch are multiples of 8: every row-major piece is 16-byte aligned in
+    // the plane. Pieces starting at or past N' and rows past M' are skipped; the piece that
+    // straddles N' carries kNone over [N', align8(N')), inside the pad fill below.
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int t = lane + 64 * k;
+      const int row = t / 7;
+      const int c = jb + 8 * (t - 7 * row);
+      if (t < kTilePieces && c < V.Np && (!PARTIAL || row < rows))
+        *(gu4*)((gchar*)(gu16*)Hr + (unsigned)(row * ldr + c) * 2u) = pr[k];
+    }
+    __builtin_amdgcn_wave_barrier();
+    // strip-major: a column's 32 prefixes in split order are the lane's 16 words, 64 B, and the
+    // block's 56 columns are 3,584 contiguous bytes of the plane: the tile again, now
+    // [column][4 pieces] (piece q of column c in slot q ^ (c >> 1 & 3): eight lanes' 16-byte
+    // writes then cover all 32 banks), read back linearly, piece t to byte 16 t of the run
+    // (the 4 x 4 DPP transpose inside lane quads that this replaces, ~64 VALU per block and
+    // 64-byte runs: sweep +0.008 ms per sub-batch, profiles/r07/README.txt)
+    if (cc >= 0) {
+      const int f = (cc >> 1) & 3;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) tq[cc * 4 + (q ^ f)] = u32x4{hw[4 * q], hw[4 * q + 1], hw[4 * q + 2], hw[4 * q + 3]};
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int t = min(lane + 64 * k, kTilePieces - 1), c = t >> 2;
+      pq[k] = tq[c * 4 + ((t & 3) ^ ((c >> 1) & 3))];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(pq[k].x), "+v"(pq[k].y), "+v"(pq[k].z), "+v"(pq[k].w));
+    __builtin_amdgcn_wave_barrier();  // the next block's tile writes stay behind these reads
+    gu16* hcb = (gu16*)(Hc + ((size_t)strip * ldc + jb) * kSR);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int t = lane + 64 * k;
+      if (t < kTilePieces && jb + (t >> 2) < V.Np) *(gu4*)((gchar*)hcb + (unsigned)t * 16u) = pq[k];
     }
   }
   // kNone over [N', align32(N')) of every row: the row select's last 32-element run then needs
   // no tail mask. After the barrier, so it lands after the walk's stores (which went to valid
-  // columns or the pad column only).
+  // columns and, in the piece that straddles N', up to align8(N')).
   __syncthreads();
   const int padw = (int)((V.Np + 31) & ~31) - V.Np;
   for (int e = threadIdx.x; e < kSR * 32; e += kThreads) {
@@ -1458,6 +1490,8 @@ __device__ __forceinline__ auto le_bits(const LT& L, unsigned Tbits, const KF& k
 constexpr int kRowsLds = 4 * (int)sizeof(WaveLds) + kSR * 64 * 4;
 // launches with lines past 2048 codes: row bits of 128 words per row
 constexpr int kRowsLds2 = 4 * (int)sizeof(WaveLds) + kSR * 128 * 4;
+// the sweep phase's four staging tiles share this LDS (one union, the phases a block barrier apart)
+static_assert(4 * kTileBytes <= kRowsLds, "the sweep's staging tiles must fit the row select's LDS");
 
 // In-register transpose of a 32 x 32 bit matrix: a[r] bit q -> a[q] bit r (stage J swaps the
 // off-diagonal J x J sub-blocks).
@@ -1599,7 +1633,10 @@ __device__ __forceinline__ void rows_body(const PairView& V, int p, int strip, c
 // KQ = 8: every line of the launch is short; KQ = 0: each pair picks its row line type (rows of
 // at most short_n codes take LineS<8>; short_n = 0 disables); KQ = 16: as 0 with LineS<16> for
 // the rest (every line <= 1024 codes); KQ = 2: as 0, and rows past 2048 codes take Line2.
-constexpr int kSweepWPE = 4;  // sweep blocks per CU (waves per SIMD)
+// sweep blocks per CU (waves per SIMD). The all-short launch is small enough for a fifth (96
+// VGPRs, 5 x 23 KB of LDS): asked for, so that the tile emit's registers do not cost it.
+template <int KQ>
+constexpr int kSweepWPE = KQ == 8 ? 5 : 4;
 // Arguments of one sweep + row-select launch (k_sweep_rows9) and of one column-select launch
 // (k_sel_cols9).
 struct SweepArgs {
@@ -1649,9 +1686,9 @@ __device__ __forceinline__ void sweep_rows_block(const SweepArgs& A, int strip, 
   if (i0 >= V.Mp || V.Np <= 0) return;
   uint16_t* Hr = K.hr + (size_t)p * kstride + (size_t)i0 * ldr;
   if (i0 + kSR <= V.Mp)
-    sweep_body_sys<false>(V, p, strip, K, ldr, ldc, kstride, Hr);
+    sweep_body_sys<false>(V, p, strip, K, ldr, ldc, kstride, Hr, smem);
   else
-    sweep_body_sys<true>(V, p, strip, K, ldr, ldc, kstride, Hr);
+    sweep_body_sys<true>(V, p, strip, K, ldr, ldc, kstride, Hr, smem);
   __syncthreads();  // the strip's F rows are complete (block-scope visibility of the global stores)
   WaveLds* wl = reinterpret_cast<WaveLds*>(smem);
   uint32_t(*rowbits)[RB] = reinterpret_cast<uint32_t(*)[RB]>(smem + 4 * sizeof(WaveLds));
@@ -1669,7 +1706,7 @@ __device__ __forceinline__ void sweep_rows_block(const SweepArgs& A, int strip, 
 }
 
 template <int KQ>
-__global__ __launch_bounds__(kThreads, kSweepWPE) void k_sweep_rows9(SweepArgs A) {
+__global__ __launch_bounds__(kThreads, kSweepWPE<KQ>) void k_sweep_rows9(SweepArgs A) {
   __shared__ __attribute__((aligned(16))) char smem[kSweepLds<KQ>];
   sweep_rows_block<KQ>(A, blockIdx.x, blockIdx.y, smem);
 }
