@@ -69,6 +69,7 @@ SIGNATURES = {
     "acoss_ftm2d_shingles": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, ctypes.c_double, ctypes.c_double, _vp, _vp],
     "acoss_ftm2d_beatsync": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.c_double, _vp, _vp, _vp],
     "acoss_ftm2d_scores": [_vp, _i32, _i32, _vp, _i64, _vp, _vp],
+    "acoss_ftm2d_topk": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "acoss_ds_finish": [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp],
     "acoss_eval_ranks": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "acoss_release_workspace": [],
@@ -828,6 +829,39 @@ def ftm2d_scores(shingles, pairs):
     rc = lib.acoss_ftm2d_scores(_ptr(S), int(S.shape[0]), int(S.shape[1]), _ptr(pairs), P, _ptr(out), _stream())
     _check(rc, "acoss_ftm2d_scores")
     return out
+
+
+FTM2D_MAX_DIM = 1024   # shingle length the pair kernels keep in registers (16 doubles per lane)
+FTM2D_MAX_TOPK = 1024  # shortlist length (ftm2d.hip keeps a query's 2k candidates in LDS)
+
+
+def ftm2d_topk(q, r, k, self_off=-1):
+    """The k best references per query without the (n_q, n_r) score matrix (acoss_ftm2d_topk):
+    q (n_q, dim) and r (n_r, dim) float64 device tensors -> (idx int32 (n_q, k), score float64
+    (n_q, k)) device tensors. Row i lists np.argsort(-scores[i], kind="stable")[:k] and those scores,
+    each exactly ftm2d_scores' for the pair; a NaN score is never listed; slots left over hold -1 /
+    NaN. self_off >= 0: query i is reference self_off + i, which is left out."""
+    torch = _torch()
+    lib = load_library()
+    for name, t in (("q", q), ("r", r)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.dim() != 2:
+            raise ValueError("%s must be a 2-D float64 device tensor" % name)
+    if q.shape[1] != r.shape[1]:
+        raise ValueError("q and r must have the same row length (%d != %d)" % (q.shape[1], r.shape[1]))
+    dim, k, self_off = int(q.shape[1]), int(k), int(self_off)
+    if not 1 <= dim <= FTM2D_MAX_DIM:
+        raise ValueError("the row length must be in [1, %d], got %d" % (FTM2D_MAX_DIM, dim))
+    if not 1 <= k <= FTM2D_MAX_TOPK:
+        raise ValueError("k must be in [1, %d], got %d" % (FTM2D_MAX_TOPK, k))
+    if self_off < -1:
+        raise ValueError("self_off must be -1 (no exclusion) or a reference row, got %d" % self_off)
+    q, r = q.contiguous(), r.contiguous()
+    n_q, n_r = int(q.shape[0]), int(r.shape[0])
+    idx = torch.empty((n_q, k), dtype=torch.int32, device="cuda")
+    score = torch.empty((n_q, k), dtype=torch.float64, device="cuda")
+    rc = lib.acoss_ftm2d_topk(_ptr(q), n_q, _ptr(r), n_r, dim, self_off, k, _ptr(idx), _ptr(score), _stream())
+    _check(rc, "acoss_ftm2d_topk")
+    return idx, score
 
 
 FINISH_MODES = {None: 0, "none": 0, "serra09": 1, "chen": 2}

@@ -3,7 +3,7 @@
 The public surface is the reference's: constructor arguments, `filepaths`, `cliques`, `N`,
 `Ds` (float32 N x N memmaps at '<cachedir>/<name>_<shortname>_<type>_dmat'),
 `load_features(i)`, `get_all_clique_ids()`, `similarity(idxs)`, `all_pairwise(parallel,
-n_cores, symmetric, precomputed)`, `cleanup_memmap()`, `getEvalStatistics(type, topsidx)`.
+n_cores, symmetric, precomputed, candidates)`, `cleanup_memmap()`, `getEvalStatistics(type, topsidx)`.
 
 What changes is how the pair loop runs (algorithm_template.py:142-193). The reference calls
 `similarity` on one pair (serial) or on 45 chunks (joblib processes). Here:
@@ -29,6 +29,9 @@ What changes is how the pair loop runs (algorithm_template.py:142-193). The refe
   * Ds is saved as '<prefix>_Ds.h5' (the reference's file, :163,193; one dataset per
     similarity type, as deepdish lays out a dict) when h5py is importable, and always as the
     '<prefix>_Ds.npz' twin; `precomputed=True` reads either back.
+  * `all_pairwise(candidates=...)` scores only the pairs an (N, k) shortlist names (FTM2D.shortlist:
+    a cheap scorer sparing an expensive one), through the same chunks, scatter, exchange and
+    finish; every other off-diagonal entry is -inf, which ranks after any score.
 Reference defects not reproduced: the NameError of parallel=True at
 :174-192 and `cleanup_memmap` calling rmtree on files (:202).
 """
@@ -200,7 +203,17 @@ class CoverAlgorithm(object):
         (P, 2) pairs; the base class has none (None: the host `similarity` loop is used)."""
         return None
 
-    def all_pairwise(self, parallel=0, n_cores=12, symmetric=False, precomputed=False):
+    # whether all_pairwise(candidates=...) is supported: not by the algorithms whose similarity-network
+    # late fusion needs dense matrices (ChenFusion, EarlyFusion)
+    _takes_candidates = True
+
+    def all_pairwise(self, parallel=0, n_cores=12, symmetric=False, precomputed=False, candidates=None):
+        """candidates: None (every pair, as the reference), or an (N, k) integer array whose row i
+        lists the songs to score song i against (-1 and i itself are ignored). symmetric=True then
+        scores the unique pairs {(min(i, j), max(i, j)) : j in candidates[i]} once each,
+        symmetric=False the ordered pairs (i, j); a scored entry holds the bits the unrestricted run
+        gives it, every other off-diagonal entry of every Ds key is -inf, the diagonal is as without
+        candidates. Ignored with precomputed=True."""
         prefix = self.get_cacheprefix()
         world, rank = _dist_info()
         if world > 1:  # before ANY "cuda" allocation, the precomputed path's evaluation included
@@ -210,8 +223,17 @@ class CoverAlgorithm(object):
             self.get_all_clique_ids()
             self._holds_Ds, self._stats_from_root = True, False
             return
+        if candidates is not None:
+            if not self._takes_candidates:
+                raise ValueError("%s scores every pair: its similarity-network late fusion needs dense "
+                                 "matrices, so `candidates` is not supported" % self.name)
+            candidates = np.asarray(candidates)
+            if candidates.ndim != 2 or candidates.shape[0] != self.N or candidates.dtype.kind not in "iu":
+                raise ValueError("candidates must be an (N, k) integer array with one row per song")
         self.prepare()
         if world > 1:
+            # the dense cost model also splits a candidate run: a stripe's share of a sparse candidate
+            # set may be uneven, but every pair is still scored once and the exchange is the same
             bounds = _dist.stripe_bounds(self.track_lengths(), world, symmetric, m=0, tau=0)
         else:
             bounds = [(0, self.N)]
@@ -219,8 +241,11 @@ class CoverAlgorithm(object):
         every = world == 1 or self._Ds_on_every_rank or self.Ds_on_every_rank
         self._holds_Ds = every or rank == 0
         self._stats_from_root = not every
-        if not self._device_all_pairwise(bounds, r0, r1, world, symmetric, every):
-            for chunk in self._pair_chunks(r0, r1, symmetric):
+        if not self._device_all_pairwise(bounds, r0, r1, world, symmetric, every, candidates):
+            if candidates is not None:
+                for key in self.Ds:
+                    self.Ds[key][r0:r1] = self._unscored_stripe(r0, r1, symmetric)
+            for chunk in self._pair_chunks(r0, r1, symmetric, candidates):
                 self.similarity(chunk)
             if world > 1:
                 self._gather_stripes(bounds, r0, r1, every)
@@ -232,16 +257,30 @@ class CoverAlgorithm(object):
         if rank == 0:
             self._save_Ds(prefix)
 
-    def _pair_chunks(self, r0, r1, symmetric):
+    def _unscored_stripe(self, r0, r1, symmetric):
+        """Rows [r0, r1) of a candidate run's matrix before any score is written: -inf where a pair
+        could be scored (j > i if symmetric, the transpose is added later; else j != i), 0 elsewhere."""
+        blk = np.full((r1 - r0, self.N), -np.inf, np.float32)
+        i, j = np.arange(r0, r1)[:, None], np.arange(self.N)[None, :]
+        blk[(j <= i) if symmetric else (j == i)] = 0.0
+        return blk
+
+    def _pair_chunks(self, r0, r1, symmetric, candidates=None):
         """The stripe's pairs in the reference's enumeration order (combinations / permutations,
-        :168-171), PAIR_CHUNK at a time, with a progress line on stderr about every 10 s (the
-        reference prints progress in its serial loop, :179-187)."""
+        :168-171), or those of them that `candidates` names, PAIR_CHUNK at a time, with a progress
+        line on stderr about every 10 s (the reference prints progress in its serial loop, :179-187)."""
         import sys
         import time
-        n_pairs = sum(self.N - i - 1 if symmetric else self.N - 1 for i in range(r0, r1))
+        if candidates is None:
+            n_pairs = sum(self.N - i - 1 if symmetric else self.N - 1 for i in range(r0, r1))
+            chunks = _dist.stripe_pair_chunks(self.N, r0, r1, symmetric, PAIR_CHUNK)
+        else:
+            pairs = _dist.candidate_pairs(candidates, r0, r1, symmetric)
+            n_pairs = len(pairs)
+            chunks = (pairs[p:p + PAIR_CHUNK] for p in range(0, n_pairs, PAIR_CHUNK))
         t0 = last = time.perf_counter()
         done = 0
-        for chunk in _dist.stripe_pair_chunks(self.N, r0, r1, symmetric, PAIR_CHUNK):
+        for chunk in chunks:
             yield chunk
             done += len(chunk)
             now = time.perf_counter()
@@ -249,7 +288,7 @@ class CoverAlgorithm(object):
                 last = now
                 print("%s: %d / %d pairs, %.1f s" % (self.name, done, n_pairs, now - t0), file=sys.stderr, flush=True)
 
-    def _device_all_pairwise(self, bounds, r0, r1, world, symmetric, every=True):
+    def _device_all_pairwise(self, bounds, r0, r1, world, symmetric, every=True, candidates=None):
         """The pair loop with the stripe kept in HBM: score chunks on the device, scatter into
         the (r1 - r0, N) stripe, one exchange (world > 1: all-gather if `every`, else a gather onto
         rank 0), symmetrise with acoss_ds_finish and copy into Ds on the ranks that receive the
@@ -258,8 +297,18 @@ class CoverAlgorithm(object):
             return False
         import torch
         from .. import _lib
-        blocks = {k: torch.zeros((r1 - r0, self.N), dtype=torch.float32, device="cuda") for k in self.Ds}
-        for chunk in self._pair_chunks(r0, r1, symmetric):
+        if candidates is None:
+            blocks = {k: torch.zeros((r1 - r0, self.N), dtype=torch.float32, device="cuda") for k in self.Ds}
+        else:  # _unscored_stripe, made on the device
+            unscored = torch.full((r1 - r0, self.N), float("-inf"), dtype=torch.float32, device="cuda")
+            if symmetric:
+                unscored.triu_(diagonal=r0 + 1)  # column > row r0 + local row stays, the rest is 0
+            else:
+                local = torch.arange(r1 - r0, device="cuda")
+                unscored[local, local + r0] = 0.0
+            blocks = {k: unscored.clone() for k in self.Ds}
+            del unscored
+        for chunk in self._pair_chunks(r0, r1, symmetric, candidates):
             sc = self._device_scores(chunk)
             p = torch.from_numpy(np.ascontiguousarray(chunk, np.int32)).pin_memory().to("cuda", non_blocking=True).long()
             for k in blocks:

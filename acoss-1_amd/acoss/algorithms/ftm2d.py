@@ -8,7 +8,9 @@ acoss_ftm2d_shingles call (ftm2d.hip: beat-synchronous float32 medians, chrompwr
 magnitudes of every 12 x WIN beat window on the f64 MFMA, per-window normalisation and log, the
 per-coefficient median over the windows; the reference does this per song in numpy, :52-66), and
 `similarity(idxs)` scores a chunk of pairs with one acoss_ftm2d_scores call.
-Ds['main'][i, j] = exp(-|s_i - s_j|^2) (:93-97).
+Ds['main'][i, j] = exp(-|s_i - s_j|^2) (:93-97). `shortlist(k)` (not in the reference) lists every
+song's k best-scoring other songs with one acoss_ftm2d_topk call, for
+`all_pairwise(candidates=...)` of an alignment scorer.
 
 Reference defects not reproduced: `os` and `dd` are used without being imported (:44,47,82), and a
 track with fewer than WIN beats crashes on None.T (:61,129-130); here such a track raises a
@@ -71,6 +73,19 @@ class FTM2D(CoverAlgorithm):
         self.prepare()
         score = _lib.ftm2d_scores(self._bank, idxs.astype(np.int32))
         self.Ds['main'][idxs[:, 0], idxs[:, 1]] = score.cpu().numpy()
+
+    def shortlist(self, k, rows=None):
+        """The k songs of largest FTM2D score for each song of rows = (r0, r1) (default: all), the
+        song itself left out, best first, equal scores by increasing index: a host (r1 - r0, k)
+        int32 array, -1 in a slot with no candidate (k > N - 1, or a silent track's NaN shingle).
+        One acoss_ftm2d_topk call over the shingle bank; the score matrix is never formed. Pass the
+        result as all_pairwise(candidates=...) of an alignment scorer on the same dataset CSV."""
+        self.prepare()
+        r0, r1 = (0, self.N) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= r0 <= r1 <= self.N:
+            raise ValueError("rows must be a range within [0, %d], got (%d, %d)" % (self.N, r0, r1))
+        idx, _ = _lib.ftm2d_topk(self._bank[r0:r1], self._bank, k, self_off=r0)
+        return idx.cpu().numpy()
 
     def _device_scores(self, idxs):
         """exp(-|s_i - s_j|^2) per pair as float32 device scores (the memmap's dtype)."""

@@ -21,6 +21,7 @@ __all__ = ["ChenFusion"]
 class ChenFusion(ChromaBackedAlgorithm):
     # the SNF late fusion runs on every rank (row-sharded): every rank needs the assembled Ds
     _Ds_on_every_rank = True
+    _takes_candidates = False  # the fusion needs every pair's score
 
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='benchmark', oti=True, kappa=0.095,
                  tau=1, m=9, downsample_fac=40, cachedir="cache"):

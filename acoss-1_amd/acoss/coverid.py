@@ -6,6 +6,8 @@ reference defects are not reproduced: "EarlyFusionTraile" d
 are batched on the GPU; with torch.distributed initialised every rank takes a stripe).
 All five names of `algorithm_names` run on the engine; FTM2D (coverid.py:107-122) makes its
 shingles in `prepare()` and scores the pairs symmetrically.
+`shortlist=k` (not in the reference) spends an alignment only on each song's k best FTM2D
+candidates: Serra09 and SiMPle score the pairs FTM2D.shortlist(k) names and leave the rest -inf.
 """
 import argparse
 import sys
@@ -18,27 +20,44 @@ __all__ = ['benchmark', 'algorithm_names']
 _LOG_FILE_PATH = "acoss.coverid.log"
 
 algorithm_names = ["Serra09", "EarlyFusionTraile", "LateFusionChen", "FTM2D", "SiMPle"]
+shortlist_algorithms = ("Serra09", "SiMPle")  # the alignment scorers that take an FTM2D shortlist
 
 
 def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09", shortname="covers80",
-              parallel=True, n_workers=-1, cachedir="cache"):
+              parallel=True, n_workers=-1, cachedir="cache", shortlist=None):
     """Run one cover-ID algorithm over a dataset CSV and print/write its evaluation statistics.
-    Returns the algorithm object (its Ds hold the similarity matrices)."""
+    Returns the algorithm object (its Ds hold the similarity matrices).
+    shortlist: None, or k: Serra09 / SiMPle score only each song's k best FTM2D candidates (shingles
+    made from the same CSV, features, chroma type and cache directory); the entries of Ds they do
+    not score are -inf."""
     logger = log(_LOG_FILE_PATH)
     if algorithm not in algorithm_names and algorithm != "EarlyFusion":
         warn = ("acoss.coverid: Couldn't find '%s' algorithm in acoss Available cover id algorithms are %s "
                 % (algorithm, str(algorithm_names)))
         logger.debug(warn)
         raise NotImplementedError(warn)
+    if shortlist is not None and algorithm not in shortlist_algorithms:
+        raise ValueError("shortlist is supported by %s only, not by '%s'"
+                         % (" and ".join(shortlist_algorithms), algorithm))
     logger.info("Running acoss cover identification benchmarking for the algorithm - '%s'" % algorithm)
     start = time.monotonic()
     kw = dict(dataset_csv=dataset_csv, datapath=feature_dir, chroma_type=feature_type, shortname=shortname,
               cachedir=cachedir)
+    candidates = None
+    if shortlist is not None:
+        from . import evaluation
+        from .algorithms.ftm2d import FTM2D
+        first = FTM2D(**kw)
+        candidates = first.shortlist(int(shortlist))
+        logger.info("FTM2D shortlist of %d per song: recall of the same-clique pairs %.4f"
+                    % (int(shortlist), evaluation.shortlist_recall(candidates, first.cliques)))
+        first.cleanup_memmap()
+        del first
     if algorithm == "Serra09":
         from .algorithms.rqa_serra09 import Serra09
         algo = Serra09(**kw)
         logger.info('Computing pairwise similarity...')
-        algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True)
+        algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True, candidates=candidates)
         algo.normalize_by_length()
     elif algorithm in ("EarlyFusionTraile", "EarlyFusion"):
         from .algorithms.earlyfusion_traile import EarlyFusion
@@ -63,7 +82,7 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         algo.prepare()
         logger.info('Feature loading done...')
         logger.info('Computing pairwise similarity...')
-        algo.all_pairwise(parallel, n_cores=n_workers, symmetric=False)
+        algo.all_pairwise(parallel, n_cores=n_workers, symmetric=False, candidates=candidates)
     else:  # "FTM2D" (coverid.py:107-122)
         from .algorithms.ftm2d import FTM2D
         algo = FTM2D(**kw)
@@ -95,10 +114,13 @@ def parser_args(cmd_args):
     parser.add_argument("-p", '--parallel', type=int, choices=(0, 1), action="store", default=1,
                         help="Accepted for compatibility")
     parser.add_argument("-n", '--n_workers', type=int, action="store", default=-1, help="Accepted for compatibility")
+    parser.add_argument("-k", '--shortlist', type=int, action="store", default=None,
+                        help="Serra09 / SiMPle: score only each song's K best FTM2D candidates")
     return parser.parse_args(cmd_args)
 
 
 if __name__ == '__main__':
     args = parser_args(sys.argv[1:])
     benchmark(dataset_csv=args.dataset_csv, feature_dir=args.feature_dir, feature_type=args.chroma_type,
-              algorithm=args.method, shortname=args.shortname, parallel=bool(args.parallel), n_workers=args.n_workers)
+              algorithm=args.method, shortname=args.shortname, parallel=bool(args.parallel), n_workers=args.n_workers,
+              shortlist=args.shortlist)

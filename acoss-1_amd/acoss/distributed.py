@@ -116,6 +116,37 @@ def stripe_pair_chunks(n, r0, r1, symmetric=True, chunk=1 << 20):
         yield np.concatenate(buf) if len(buf) > 1 else buf[0]
 
 
+def candidate_pairs(cands, r0, r1, symmetric=True):
+    """The pairs of row stripe [r0, r1) that an (N, k) candidate array names, as (P, 2) int32 in
+    lexicographic (i, j) order: stripe_pairs' order restricted to the subset. Row i of `cands` lists
+    song i's candidates; entries of -1 and j == i are ignored, repeats count once.
+    symmetric: the unique pairs (min(i, j), max(i, j)) over all rows, each owned by the stripe of its
+    smaller index (so a row's pairs also come from the rows that list it); else the ordered pairs
+    (i, j), j in cands[i], of the stripe's rows. The list is formed whole: at most N k pairs
+    (1.5 10^6 for a Da-TACOS shortlist of 100), not the 10^8 of a dense stripe."""
+    c = np.asarray(cands)
+    if c.ndim != 2 or c.dtype.kind not in "iu":
+        raise ValueError("candidates must be an (N, k) integer array")
+    n = c.shape[0]
+    c = c.astype(np.int64)
+    if c.size and (c.min() < -1 or c.max() >= n):
+        raise ValueError("candidate entries must be -1 or lie in [0, %d)" % n)
+    if symmetric:
+        i = np.repeat(np.arange(n, dtype=np.int64), c.shape[1])
+        j = c.reshape(-1)
+    else:
+        i = np.repeat(np.arange(r0, r1, dtype=np.int64), c.shape[1])
+        j = c[r0:r1].reshape(-1)
+    keep = (j >= 0) & (j != i)
+    i, j = i[keep], j[keep]
+    if symmetric:
+        i, j = np.minimum(i, j), np.maximum(i, j)
+        keep = (i >= r0) & (i < r1)
+        i, j = i[keep], j[keep]
+    key = np.unique(i * n + j)  # sorted: lexicographic in (i, j)
+    return np.stack([key // max(n, 1), key % max(n, 1)], 1).astype(np.int32)
+
+
 def scatter_stripe(pairs, scores, r0, r1, n):
     """Local (r1-r0, n) block with the stripe's scores (zeros elsewhere, as the memmap)."""
     import torch

@@ -134,6 +134,27 @@ def eval_statistics_device(D, labels=None, cliques=None, topsidx=(1, 10, 100, 10
     return _stats_from_ranks(member_ranks, Ks, N, topsidx)
 
 
+def shortlist_recall(cands, cliques):
+    """Fraction of the ordered same-clique pairs (i, j), i != j, with j in cands[i]: what a shortlist
+    (FTM2D.shortlist, an (N, k) array, -1 = empty slot) keeps of the pairs the evaluation looks for,
+    the number to read when choosing k. cliques: lists (or sets) of song indices, or the
+    {label: members} dict of CoverAlgorithm.cliques. NaN when no clique has two songs."""
+    cands = np.asarray(cands)
+    if isinstance(cliques, dict):
+        cliques = list(cliques.values())
+    hit = total = 0
+    for c in cliques:
+        members = np.array(sorted(c), dtype=np.int64)
+        if len(members) < 2:
+            continue
+        rows = cands[members]                                  # (K, k)
+        listed = np.isin(rows, members) & (rows != members[:, None])
+        # a repeated candidate counts once
+        hit += sum(len(np.unique(r[m])) for r, m in zip(rows, listed))
+        total += len(members) * (len(members) - 1)
+    return hit / total if total else float("nan")
+
+
 def write_results_csv(resultsfile, name, similarity_type, stats, topsidx=(1, 10, 100, 1000)):
     """Append one row in the reference's results CSV format (algorithm_template.py:277-290)."""
     MR, MRR, MDR, MAP, tops = stats

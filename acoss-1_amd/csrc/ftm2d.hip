@@ -25,6 +25,10 @@
 //   k_ftm_scores     exp(-sum (s1 - s2)^2) per pair (:93-96), one wave per pair, the differences
 //                    summed in one fixed order; the query shingle stays in registers over
 //                    consecutive pairs that share it.
+//   k_ftm_topk       the same scores fused with a per-query k-best selection (not in the reference:
+//                    the shortlist that spares the alignment scorers); four queries per wave in
+//                    registers, each reference row read once for all four, the running k best of a
+//                    query in LDS; the query x reference scores are never stored.
 // Every per-track result depends on that track's data only (fixed summation orders, exact sorts),
 // so a track's shingle does not depend on the batch it is computed in.
 #include <cmath>
@@ -381,6 +385,205 @@ __global__ __launch_bounds__(256) void k_ftm_scores(const double* __restrict__ s
   }
 }
 
+// ---- fused score + k best per query (acoss_ftm2d_topk) ----
+// One wave per block owns kTopkQ consecutive queries, their shingles in registers, and walks over
+// every reference row once, so a row read serves all of them. Per pair the lane sums are
+// k_ftm_scores' (64 lane-strided partial sums in increasing d; a lane past dim adds 0 * 0, which
+// leaves a non-negative sum unchanged), and so is every addition of the xor butterfly: at offset 32
+// the lanes below 32 go on with queries 0 and 2 and send their halves of 1 and 3, at offset 16 the
+// lanes with bit 4 clear go on with 0 / 1, and offsets 8..1 run on the one value left, which lane L
+// then holds for query topk_slot(L). Sixteen rows fill one register (row = L & 15), exp runs once
+// on it, and whatever beats the query's threshold (the k-th best score as of its last compaction,
+// -inf before) is appended to the query's LDS list of `cap` >= 2k entries. A list that cannot take
+// a tile's candidates is sorted by (score descending, index ascending) and cut to k first. Rows
+// come in increasing index, so a later row that only ties the threshold can never be among the k
+// best; NaN compares false and is never appended.
+// A table with few queries would leave most of the GPU idle (n_q / 4 waves, each walking every
+// row), so the reference rows are then split into gridDim.y contiguous ranges: block (b, y) lists
+// the k best of range y into a partial list, and k_ftm_topk_merge, one wave per query, streams the
+// query's partial lists in range order through the same threshold, append and compaction. Range
+// order is index order between lists, and a list is sorted, so "a later entry that only ties the
+// threshold is never among the k best" still holds.
+constexpr int kTopkQ = 4;
+constexpr int kTopkRows = 16;
+constexpr int kMaxTopk = 1024;
+constexpr int kTopkWaves = 2048;    // waves wanted in flight: two per SIMD of 256 CUs
+constexpr int kTopkMaxSplits = 16;  // reference ranges at most (the partial lists are n_q x splits x k)
+
+__device__ __forceinline__ int topk_slot(int lane) { return ((lane >> 5) & 1) | ((lane >> 3) & 2); }
+
+// Sort the list (cnt entries of cap, a power of two) and keep the k best. Whole wave, uniform.
+__device__ __forceinline__ void topk_compact(double* S, int* J, int cap, int k, int lane, int& cnt, double& thr) {
+  for (int e = cnt + lane; e < cap; e += 64) {
+    S[e] = -__builtin_inf();
+    J[e] = 0x7fffffff;
+  }
+  __syncthreads();
+  for (int kk = 2; kk <= cap; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int p = lane; p < (cap >> 1); p += 64) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), x = i | j;
+        const double a = S[i], b = S[x];
+        const int ja = J[i], jb = J[x];
+        const bool b_first = b > a || (b == a && jb < ja);
+        if (b_first == ((i & kk) == 0)) {
+          S[i] = b;
+          S[x] = a;
+          J[i] = jb;
+          J[x] = ja;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  cnt = min(cnt, k);
+  thr = cnt == k ? S[k - 1] : -__builtin_inf();
+}
+
+// grid (ceil(n_q / 4), splits): block (b, y) lists queries 4 b .. 4 b + 3 against reference rows
+// [y split_rows, (y + 1) split_rows) into row (q splits + y) of the outputs
+__global__ __launch_bounds__(64) void k_ftm_topk(const double* __restrict__ qs, int n_q, const double* __restrict__ rs,
+                                                 int n_r, int dim, int self_off, int k, int cap, int split_rows,
+                                                 int32_t* __restrict__ idx_out, double* __restrict__ score_out) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  double* S = sm;                                         // [kTopkQ][cap]
+  int* J = reinterpret_cast<int*>(sm + kTopkQ * cap);     // [kTopkQ][cap]
+  const int lane = threadIdx.x;
+  const int q0 = blockIdx.x * kTopkQ;
+  const int jb = min(n_r, (int)blockIdx.y * split_rows), je = min(n_r, jb + split_rows);
+  const int slot = topk_slot(lane), row = lane & (kTopkRows - 1);
+  double q[kTopkQ][kMaxDim / 64];
+#pragma unroll
+  for (int a = 0; a < kTopkQ; ++a) {
+    const double* Q = qs + (size_t)min(q0 + a, n_q - 1) * dim;  // a query past the table repeats the last, unlisted
+#pragma unroll
+    for (int u = 0; u < kMaxDim / 64; ++u) q[a][u] = lane + 64 * u < dim ? Q[lane + 64 * u] : 0.0;
+  }
+  // the lane's own query: never its own song, never a query past the table
+  const int self_j = self_off >= 0 ? self_off + q0 + slot : -1;
+  const bool q_ok = q0 + slot < n_q;
+  int cnt[kTopkQ];
+  double thr[kTopkQ];
+#pragma unroll
+  for (int a = 0; a < kTopkQ; ++a) {
+    cnt[a] = 0;
+    thr[a] = -__builtin_inf();
+  }
+  double thr_l = -__builtin_inf();  // thr[slot]
+  double rn[kMaxDim / 64];
+#pragma unroll
+  for (int u = 0; u < kMaxDim / 64; ++u)
+    rn[u] = (jb < je && lane + 64 * u < dim) ? rs[(size_t)jb * dim + lane + 64 * u] : 0.0;
+  for (int j0 = jb; j0 < je; j0 += kTopkRows) {
+    double d2 = __builtin_nan("");  // rows past the range stay NaN
+    const int nj = min(kTopkRows, je - j0);
+    for (int jj = 0; jj < nj; ++jj) {
+      double r[kMaxDim / 64];
+#pragma unroll
+      for (int u = 0; u < kMaxDim / 64; ++u) r[u] = rn[u];
+      if (j0 + jj + 1 < je) {  // the next row's loads fly under this row's arithmetic
+        const double* R = rs + (size_t)(j0 + jj + 1) * dim;
+#pragma unroll
+        for (int u = 0; u < kMaxDim / 64; ++u) rn[u] = lane + 64 * u < dim ? R[lane + 64 * u] : 0.0;
+      }
+      double acc[kTopkQ];
+#pragma unroll
+      for (int a = 0; a < kTopkQ; ++a) acc[a] = 0.0;
+#pragma unroll
+      for (int u = 0; u < kMaxDim / 64; ++u)
+        if (64 * u < dim) {  // uniform
+#pragma unroll
+          for (int a = 0; a < kTopkQ; ++a) {
+            const double d = q[a][u] - r[u];
+            acc[a] = acc[a] + d * d;
+          }
+        }
+      const bool hi32 = lane & 32, hi16 = lane & 16;
+      const double x01 = (hi32 ? acc[1] : acc[0]) + __shfl_xor(hi32 ? acc[0] : acc[1], 32);
+      const double x23 = (hi32 ? acc[3] : acc[2]) + __shfl_xor(hi32 ? acc[2] : acc[3], 32);
+      double y = (hi16 ? x23 : x01) + __shfl_xor(hi16 ? x01 : x23, 16);
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) y = y + __shfl_xor(y, o);
+      d2 = row == jj ? y : d2;
+    }
+    const double s = exp(-d2);
+    const int j = j0 + row;
+    const bool pass = q_ok && j != self_j && s > thr_l;
+    const unsigned long long m_all = __ballot(pass);
+    if (m_all == 0) continue;  // uniform
+#pragma unroll
+    for (int a = 0; a < kTopkQ; ++a) {
+      // slot a's lanes: 16 consecutive ones starting at 32 (a & 1) + 16 (a >> 1)
+      const unsigned long long m = m_all & (0xffffull << (32 * (a & 1) + 16 * (a >> 1)));
+      if (m == 0) continue;  // uniform
+      const int n = __popcll(m);
+      double* Sa = S + a * cap;
+      int* Ja = J + a * cap;
+      if (cnt[a] + n > cap) {
+        topk_compact(Sa, Ja, cap, k, lane, cnt[a], thr[a]);
+        thr_l = slot == a ? thr[a] : thr_l;
+      }
+      if (pass && slot == a) {
+        const int pos = cnt[a] + __popcll(m & ((1ull << lane) - 1ull));
+        Sa[pos] = s;
+        Ja[pos] = j;
+      }
+      cnt[a] += n;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < kTopkQ; ++a) {
+    if (q0 + a >= n_q) break;  // uniform
+    double* Sa = S + a * cap;
+    int* Ja = J + a * cap;
+    __syncthreads();
+    topk_compact(Sa, Ja, cap, k, lane, cnt[a], thr[a]);
+    for (int t = lane; t < k; t += 64) {
+      const size_t o = ((size_t)(q0 + a) * gridDim.y + blockIdx.y) * k + t;
+      idx_out[o] = t < cnt[a] ? Ja[t] : -1;
+      score_out[o] = t < cnt[a] ? Sa[t] : __builtin_nan("");
+    }
+  }
+}
+
+// One wave per query: the n_parts sorted partial lists of k entries each (idx -1 = empty slot), in
+// range order, 64 entries at a time through the threshold, into one list of cap >= k + 64 entries.
+__global__ __launch_bounds__(64) void k_ftm_topk_merge(const int32_t* __restrict__ part_idx,
+                                                       const double* __restrict__ part_score, int n_parts, int k,
+                                                       int cap, int32_t* __restrict__ idx_out,
+                                                       double* __restrict__ score_out) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  double* S = sm;                               // [cap]
+  int* J = reinterpret_cast<int*>(sm + cap);    // [cap]
+  const int lane = threadIdx.x, total = n_parts * k;
+  const size_t base = (size_t)blockIdx.x * total;
+  int cnt = 0;
+  double thr = -__builtin_inf();
+  for (int e0 = 0; e0 < total; e0 += 64) {
+    const int e = e0 + lane;
+    const int j = e < total ? part_idx[base + e] : -1;
+    const double s = e < total ? part_score[base + e] : __builtin_nan("");
+    const bool pass = j >= 0 && s > thr;
+    const unsigned long long m = __ballot(pass);
+    if (m == 0) continue;  // uniform
+    const int n = __popcll(m);
+    if (cnt + n > cap) topk_compact(S, J, cap, k, lane, cnt, thr);
+    if (pass) {
+      const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
+      S[pos] = s;
+      J[pos] = j;
+    }
+    cnt += n;
+  }
+  __syncthreads();
+  topk_compact(S, J, cap, k, lane, cnt, thr);
+  for (int t = lane; t < k; t += 64) {
+    const size_t o = (size_t)blockIdx.x * k + t;
+    idx_out[o] = t < cnt ? J[t] : -1;
+    score_out[o] = t < cnt ? S[t] : __builtin_nan("");
+  }
+}
+
 // Twiddles, built once: for the frequency tile kt, row kk and column li the pair (re, im) that Z's
 // part kk contributes to F[k = 16 kt + li]: F = sum_t (Zr + i Zi)(cos - i sin)(2 pi k t / 75), so
 // Zr[t] adds (cos, -sin) and Zi[t] adds (sin, cos). The angle table is filled from m = 0..37 and
@@ -539,5 +742,56 @@ extern "C" int acoss_ftm2d_scores(const double* shingles, int32_t n_tracks, int3
                      n_pairs, scores_out);
   ACOSS_LAUNCH_CHECK();
   prof_end(PH_FTM_SCORES, s);
+  return ACOSS_OK;
+}
+
+extern "C" int acoss_ftm2d_topk(const double* q_shingles, int32_t n_q, const double* r_shingles, int32_t n_r,
+                                int32_t dim, int32_t self_off, int32_t k, int32_t* idx_out, double* score_out,
+                                void* hip_stream) {
+  clear_error();
+  if (dim < 1 || dim > kMaxDim || k < 1 || k > kMaxTopk) {
+    set_error("acoss_ftm2d_topk: bad arguments (dim must be in [1, %d] and k in [1, %d]; got dim=%d, k=%d)", kMaxDim,
+              kMaxTopk, dim, k);
+    return ACOSS_E_ARG;
+  }
+  if (n_q < 0 || n_r < 0 || self_off < -1 ||
+      (n_q > 0 && (!q_shingles || !idx_out || !score_out || (n_r > 0 && !r_shingles)))) {
+    set_error("acoss_ftm2d_topk: bad arguments (negative count, self_off < -1 or a null table)");
+    return ACOSS_E_ARG;
+  }
+  if (n_q == 0) return ACOSS_OK;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  int cap = 32;  // a power of two (bitonic sort) that takes k kept entries and a tile's 16 new ones
+  while (cap < 2 * k) cap <<= 1;
+  const size_t lds = (size_t)kTopkQ * cap * (sizeof(double) + sizeof(int));  // at most 96 KiB (k > 512)
+  if (lds > 64 * 1024)
+    ACOSS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ftm_topk),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // few queries: split the reference rows over up to kTopkMaxSplits blocks per query group, ranges
+  // of whole 16-row tiles, until about kTopkWaves waves are in flight; then merge the partial lists
+  const int blocks = (n_q + kTopkQ - 1) / kTopkQ;
+  const int tiles = (n_r + kTopkRows - 1) / kTopkRows;
+  int splits = std::max(1, std::min(std::min(kTopkMaxSplits, tiles), kTopkWaves / blocks));
+  const int split_rows = std::max(1, (tiles + splits - 1) / splits) * kTopkRows;
+  splits = std::max(1, (n_r + split_rows - 1) / split_rows);  // no empty range
+  int32_t* pidx = idx_out;
+  double* pscore = score_out;
+  if (splits > 1) {  // partial lists: n_q x splits x k (score, index) entries
+    const size_t n_part = (size_t)n_q * splits * k;
+    char* ws = static_cast<char*>(workspace(21, n_part * (sizeof(double) + sizeof(int32_t))));
+    if (!ws) return ACOSS_E_HIP;
+    pscore = reinterpret_cast<double*>(ws);
+    pidx = reinterpret_cast<int32_t*>(ws + n_part * sizeof(double));
+  }
+  hipLaunchKernelGGL(k_ftm_topk, dim3((unsigned)blocks, (unsigned)splits), dim3(64), lds, s, q_shingles, n_q,
+                     r_shingles, n_r, dim, self_off, k, cap, split_rows, pidx, pscore);
+  ACOSS_LAUNCH_CHECK();
+  if (splits > 1) {
+    int mcap = 128;  // k kept entries and a round's 64 new ones
+    while (mcap < 2 * k) mcap <<= 1;
+    hipLaunchKernelGGL(k_ftm_topk_merge, dim3((unsigned)n_q), dim3(64), (size_t)mcap * (sizeof(double) + sizeof(int)),
+                       s, pidx, pscore, splits, k, mcap, idx_out, score_out);
+    ACOSS_LAUNCH_CHECK();
+  }
   return ACOSS_OK;
 }

@@ -223,6 +223,21 @@ int acoss_ftm2d_beatsync(const float* feats, const int64_t* track_off, const int
 int acoss_ftm2d_scores(const double* shingles, int32_t n_tracks, int32_t dim, const int32_t* pairs, int64_t n_pairs,
                        double* scores_out, void* hip_stream);
 
+/* FTM2D shortlist: for query row q of q_shingles (n_q x dim) the k rows j of r_shingles (n_r x dim)
+ * of largest score exp(-sum_d (s_q[d] - s_j[d])^2), in decreasing score order, equal scores by
+ * increasing j: idx_out[q] = np.argsort(-row, kind="stable")[:k] of the score row, score_out[q] the
+ * scores, each bit for bit what acoss_ftm2d_scores returns for that pair (same summation order).
+ * The n_q x n_r scores are never stored: the k best of a query live in LDS while its wave walks
+ * over the reference rows (with few queries the rows are split into up to 16 ranges whose partial
+ * lists, n_q x ranges x k entries of workspace, are merged by a second kernel). self_off >= 0: query q is reference row self_off + q, which is left
+ * out (a rank passes its row stripe as the queries and its first row as self_off); -1: nothing is
+ * left out. A pair whose score is NaN is never listed; slots left over (fewer than k candidates,
+ * or a NaN query row) hold idx -1 and score NaN. idx_out int32, score_out float64, both (n_q x k).
+ * dim in [1, 1024], k in [1, 1024] (ACOSS_E_ARG otherwise); the two tables may be the same buffer. */
+int acoss_ftm2d_topk(const double* q_shingles, int32_t n_q, const double* r_shingles, int32_t n_r, int32_t dim,
+                     int32_t self_off, int32_t k, int32_t* idx_out /* n_q x k */, double* score_out /* n_q x k */,
+                     void* hip_stream);
+
 /* Batched EarlyFusion scores (A15: EarlyFusion.similarity, acoss/algorithms/earlyfusion_traile.py:157-198).
  * Block features of every track packed row-major: mfcc (sum nb x d_mfcc), ssm (sum nb x d_ssm),
  * chroma (sum nb x d_chroma, 12-bin blocks) float32, track t's rows at block_off[t], n_blocks[t]
