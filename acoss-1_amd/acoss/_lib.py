@@ -47,6 +47,8 @@ SIGNATURES = {
     "acoss_crp_align": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _vp],
     "acoss_crp_pair": [_vp, _i32, _vp, _i32, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _vp, _vp, _vp],
     "acoss_align_crp": [_vp, _i32, _i32, _i32, _f32, _f32, _vp, _vp],
+    "acoss_crp_locate": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _vp],
+    "acoss_locate_crp": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
     "acoss_sw_constrained": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "acoss_csm": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "acoss_get_oti": [_vp, _vp, _i32, _vp, _vp],
@@ -252,6 +254,40 @@ def align_crp(C, align=0, gamma_open=0.5, gamma_ext=0.5):
                              float(gamma_ext), _ptr(out), _stream())
     _check(rc, "acoss_align_crp")
     return out
+
+
+def crp_locate(feats, track_off, track_len, max_len, pairs, params):
+    """Batched Qmax with its location (acoss_crp_locate): inputs as crp_align. Returns device tensors
+    {"qmax" (P,) f32, "seg" (P, 4) i32 = (i0, j0, i1, j1) in stacked-frame rows / columns, (-1, -1, -1, -1)
+    where Qmax is 0, "oti" (P,) i32}."""
+    torch = _torch()
+    lib = load_library()
+    feats = _dev(feats, torch.float32)
+    track_off = _dev(track_off, torch.int64)
+    track_len = _dev(track_len, torch.int32)
+    pairs, _ = _pairs_dev(pairs, int(track_len.shape[0]))
+    P = pairs.shape[0]
+    q = torch.empty(P, dtype=torch.float32, device="cuda")
+    seg = torch.empty((P, 4), dtype=torch.int32, device="cuda")
+    o = torch.empty(P, dtype=torch.int32, device="cuda")
+    rc = lib.acoss_crp_locate(_ptr(feats), _ptr(track_off), _ptr(track_len), int(track_len.shape[0]), int(max_len),
+                              _ptr(pairs), int(P), ctypes.byref(params), _ptr(q), _ptr(seg), _ptr(o), _stream())
+    _check(rc, "acoss_crp_locate")
+    return {"qmax": q, "seg": seg, "oti": o}
+
+
+def locate_crp(C, gamma_open=0.5, gamma_ext=0.5):
+    """Qmax of a binary (M, N) matrix and where it lies (acoss_locate_crp): (score (1,) f32,
+    seg (4,) i32 = (i0, j0, i1, j1)) device tensors; the score is align_crp(C, 0, ...)'s."""
+    torch = _torch()
+    lib = load_library()
+    C = _dev(C, torch.uint8)
+    out = torch.empty(1, dtype=torch.float32, device="cuda")
+    seg = torch.empty(4, dtype=torch.int32, device="cuda")
+    rc = lib.acoss_locate_crp(_ptr(C), int(C.shape[0]), int(C.shape[1]), float(gamma_open), float(gamma_ext),
+                              _ptr(out), _ptr(seg), _stream())
+    _check(rc, "acoss_locate_crp")
+    return out, seg
 
 
 def _pack_mats(mats, dtype):

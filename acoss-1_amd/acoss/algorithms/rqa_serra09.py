@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 from .. import _lib
-from ..engine import ChromaBank
+from ..engine import ChromaBank, segment_frames
 from .algorithm_template import CoverAlgorithm
 
 __all__ = ["Serra09", "ChromaBackedAlgorithm"]
@@ -33,6 +33,7 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
         self.downsample_fac = downsample_fac
         self.all_feats = {}  # i -> downsampled chroma (n_i, 12) float32, as the reference caches
         self._bank = None
+        self._n_frames = None  # frames of chroma_type per song before downsampling (prepare)
 
     def _downsample(self, chromas):
         from ..synthetic import pack
@@ -52,6 +53,7 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
         if self._prepared:
             return
         chromas = [f[self.chroma_type] for f in self.load_features_many((self.chroma_type,))]
+        self._n_frames = np.array([len(c) for c in chromas], np.int64)
         out, out_off, out_len = self._downsample(chromas)
         host = out.cpu().numpy()
         for i in range(self.N):
@@ -70,6 +72,22 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
 
     def _score(self, idxs, dmax=False):
         return {k: v.cpu().numpy() for k, v in self._score_dev(idxs, dmax).items()}
+
+    def localize(self, idxs):
+        """Where the Qmax alignment of every (query, reference) pair of idxs lies: a dict of host
+        arrays 'qmax' (P,), 'oti' (P,), 'cells' (P, 4) = (i0, j0, i1, j1) in stacked-frame rows and
+        columns of the pair's CRP, and 'query_frames' / 'reference_frames' (P, 2): half-open ranges
+        in frames of `chroma_type` before downsampling (engine.segment_frames). A pair whose Qmax
+        is 0 has cells (-1, -1, -1, -1) and ranges (-1, -1). Not collective: a rank localises the
+        pairs it is given."""
+        self.prepare()
+        idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
+        r = self._bank.crp_locate(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti)
+        cells = r["seg"].cpu().numpy()
+        qf, rf = segment_frames(cells, self.m, self.tau, self.downsample_fac, self._n_frames[idxs[:, 0]],
+                                self._n_frames[idxs[:, 1]])
+        return {"qmax": r["qmax"].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": cells,
+                "query_frames": qf, "reference_frames": rf}
 
     def _norm_factors(self):
         """sqrt(n_j) in float64, n_j = downsampled frames of song j."""

@@ -19,6 +19,28 @@ def stacked_len(n, m=9, tau=1):
     return 0 if n <= inc else (n - inc + tau - 1) // tau
 
 
+def segment_frames(seg, m, tau, factor, n_query, n_reference):
+    """Cells of located alignments -> half-open ranges of original feature frames (pure numpy).
+    seg: (P, 4) (i0, j0, i1, j1) in stacked-frame rows (query) and columns (reference); n_query,
+    n_reference: (P,) (or scalar) frame counts of the tracks before downsampling by `factor`.
+    Stacked row i covers the downsampled frames i*tau .. (i + m - 1)*tau and downsampled frame d
+    the original frames [d*factor, min((d + 1)*factor, n)), so the query range is
+    [i0*tau*factor, min(((i1 + m - 1)*tau + 1)*factor, n_query)) and the reference range the same
+    in j. Returns (query_frames (P, 2), reference_frames (P, 2)) int64; an empty segment
+    (-1, -1, -1, -1) maps to (-1, -1) in both."""
+    seg = np.asarray(seg, np.int64).reshape(-1, 4)
+    P = len(seg)
+    out = []
+    for a, b, n in ((seg[:, 0], seg[:, 2], n_query), (seg[:, 1], seg[:, 3], n_reference)):
+        n = np.broadcast_to(np.asarray(n, np.int64), (P,))
+        lo = a * tau * factor
+        hi = np.minimum(((b + m - 1) * tau + 1) * factor, n)
+        r = np.stack([lo, hi], 1)
+        r[seg[:, 0] < 0] = -1
+        out.append(r)
+    return out[0], out[1]
+
+
 class ChromaBank:
     """12-bin chroma of a whole corpus resident on the current GPU."""
 
@@ -40,16 +62,15 @@ class ChromaBank:
         self.max_len = int(self.lens.max()) if len(self.lens) else 0
         self.len = torch.as_tensor(self.lens).cuda()
 
-    def crp_align(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, qmax=True,
-                  dmax=False, want_oti=False):
-        """Serra09 (Qmax) / Chen (dmax) scores for (query, reference) pairs."""
+    def _pairs(self, pairs, m, tau):
+        """(P, 2) pairs as the scorers take them, None if there are none; raises for a pair that
+        holds a track too short for the frame stacking."""
         torch = _lib._torch()
-        # host pairs stay on the host until _lib.crp_align checks them there and uploads them
-        # without a stream synchronisation (chunk after chunk keeps the GPU busy)
+        # host pairs stay on the host until _lib checks them there and uploads them without a
+        # stream synchronisation (chunk after chunk keeps the GPU busy)
         pairs = np.asarray(pairs, np.int32).reshape(-1, 2) if not isinstance(pairs, torch.Tensor) else pairs
         if (pairs.size if isinstance(pairs, np.ndarray) else pairs.numel()) == 0:
-            z = torch.zeros(0, dtype=torch.float32, device="cuda")
-            return {k: z for k, on in (("qmax", qmax), ("dmax", dmax), ("oti", want_oti)) if on}
+            return None
         short = []
         if stacked_len(int(self.lens.min()), m, tau) <= 0:  # only then can a pair hold a short track
             hp = pairs if isinstance(pairs, np.ndarray) else pairs.cpu().numpy()
@@ -57,6 +78,28 @@ class ChromaBank:
         if short:
             raise ValueError("tracks %s are too short for frameStackSize=%d, frameStackStride=%d (essentia raises)"
                              % (short[:5], m, tau))
+        return pairs
+
+    def crp_align(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, qmax=True,
+                  dmax=False, want_oti=False):
+        """Serra09 (Qmax) / Chen (dmax) scores for (query, reference) pairs."""
+        torch = _lib._torch()
+        pairs = self._pairs(pairs, m, tau)
+        if pairs is None:
+            z = torch.zeros(0, dtype=torch.float32, device="cuda")
+            return {k: z for k, on in (("qmax", qmax), ("dmax", dmax), ("oti", want_oti)) if on}
         params = _lib.crp_params(m, tau, kappa, oti, gamma_open, gamma_ext)
         return _lib.crp_align(self.feats, self.off, self.len, self.max_len, pairs, params, qmax=qmax,
                               dmax=dmax, oti=want_oti)
+
+    def crp_locate(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5):
+        """Qmax of (query, reference) pairs and where it lies: {"qmax", "seg" (P, 4), "oti"} device
+        tensors (see _lib.crp_locate); the scores are crp_align's."""
+        torch = _lib._torch()
+        pairs = self._pairs(pairs, m, tau)
+        if pairs is None:
+            return {"qmax": torch.zeros(0, dtype=torch.float32, device="cuda"),
+                    "seg": torch.zeros((0, 4), dtype=torch.int32, device="cuda"),
+                    "oti": torch.zeros(0, dtype=torch.int32, device="cuda")}
+        params = _lib.crp_params(m, tau, kappa, oti, gamma_open, gamma_ext)
+        return _lib.crp_locate(self.feats, self.off, self.len, self.max_len, pairs, params)

@@ -25,6 +25,8 @@
 //  * k_crp_dp: one wave per pair. Lane l owns 32 rows of a 2048-row band and sweeps the
 //    columns skewed by one column per lane (anti-diagonal wavefront); the two boundary rows
 //    pass down one lane per step with __shfl_up; bands chain through a small HBM buffer.
+//  * k_crp_dp_trace: the serra09 DP again, every cell also carrying the cell where its path
+//    began, for acoss_crp_locate / acoss_locate_crp (where the Qmax alignment starts and ends).
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -925,6 +927,257 @@ __global__ __launch_bounds__(64) void k_crp_dp_pk(const uint32_t* __restrict__ m
   if (lane == 0) out[p] = r;
 }
 
+// --------------------------------------------------------------------------------------
+// k_crp_dp_trace<EQG, R>: the serra09 DP of k_crp_dp<0, ., R> with ORIGIN PROPAGATION: every
+// cell carries, beside its score, the packed cell (i0 << 16) | j0 where its path began, and the
+// wave reduces (Qmax, end cell, origin of the end cell) instead of a bare maximum. Memory per
+// pair stays O(1) beyond the DP's own: no M' x N' score matrix is written.
+//  * predecessors in the fixed order a = (i-1, j-1), b = (i-2, j-1), c = (i-1, j-2); the origin is
+//    that of the FIRST predecessor attaining the maximum (raw values on a hit, penalised values
+//    on a miss; a strictly greater value replaces, an equal one does not); a hit whose
+//    predecessors are all 0 starts a path at itself.
+//  * the end cell is the first cell in row-major order holding Qmax. The skewed walk does not
+//    visit cells in row-major order, so every update compares the packed end key (i << 16) | j:
+//    v > best || (v == best && v > 0 && key < bestkey). Inside one step a lane's cells share a
+//    column and come in ascending rows, so there "first wins" is the strict compare alone.
+//  * general arithmetic, validity per cell (any gamma). EQG = true is launched only where
+//    gamma_open == gamma_ext = K/2 (K a small non-negative integer): every score is then an exact
+//    multiple of 1/2, x - gamma never rounds, and the first maximum of the penalised values is the
+//    first maximum of the raw ones, so one select serves hit and miss. Origins are defined where
+//    a path can only begin on a hit, i.e. for gamma >= 0.
+//  * R = 8 rows per lane for CRPs of at most 512 rows, R = 16 above (bands of 64 R rows): three
+//    rotating columns of R scores and R origins are 6 R live registers. A launch takes the pairs
+//    with row_lo < M' <= row_hi and leaves the others to the launch of the other R.
+//  * the values handed to the next lane, and across a band boundary through HBM, are the last two
+//    rows' scores, CRP bits and origins (TraceRec).
+// Every lane runs every step and selects; the only branches around a shuffle are wave-uniform.
+// --------------------------------------------------------------------------------------
+struct DpAboveT {   // what lane l-1 (or the band above) hands down for one column
+  float q30, q31;   // scores of its last two rows (R-2, R-1)
+  uint32_t b;       // bit0 = C[row R-2], bit1 = C[row R-1]
+  uint32_t o30, o31;  // origins of the same two cells
+};
+
+struct TraceRec {  // one column of a band boundary, 32 B
+  float4 q;        // q30, q31, bits as float, unused
+  uint4 o;         // o30, o31, unused
+};
+
+template <bool EQG, int R>
+struct DpLaneT {
+  static_assert(R <= 16, "the extended CRP words are 32-bit");
+  float go, ge;
+  int Np;
+  uint32_t rowvalid;  // bit r: 2 <= global row < Mp
+  uint32_t key0;      // (global row of this lane's row 0) << 16
+  uint32_t w1, w2;    // CRP words of columns c-1, c-2 (bit r = row r)
+  DpAboveT h1, h2;    // from above for columns c-1, c-2
+  float best;         // this lane's maximum so far, its end key and the origin of that cell
+  uint32_t bkey, borg;
+
+  // (qn, on): new column c; (q1, o1): column c-1; (q2, o2): column c-2.
+  __device__ __forceinline__ DpAboveT step(float (&qn)[R], uint32_t (&on)[R], const float (&q1)[R],
+                                           const uint32_t (&o1)[R], const float (&q2)[R], const uint32_t (&o2)[R],
+                                           uint32_t w0, const DpAboveT& h0, int c) {
+    const bool colvalid = (c >= 2) && (c < Np);
+    const uint32_t vmask = colvalid ? rowvalid : 0u;
+    // extended words: bit r+2 <-> row r; bits 0,1 <-> rows -2,-1 (from above)
+    const uint32_t e0 = (w0 << 2) | h0.b;
+    const uint32_t e1 = (w1 << 2) | h1.b;
+    const uint32_t e2 = (w2 << 2) | h2.b;
+    const uint32_t kc = key0 + (uint32_t)c;  // key of (row 0, c); only used where colvalid
+    const float g_open = go, g_ext = ge;     // by value: a select between members is a select of addresses
+    auto gam = [&](uint32_t bit) { return bit ? g_open : g_ext; };
+    float cb = 0.0f;                         // this column's first maximum, its key and origin
+    uint32_t ck = 0u, co = 0u;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float Qa = r >= 1 ? q1[r - 1] : h1.q31;                        // Q[r-1][c-1]
+      const float Qb = r >= 2 ? q1[r - 2] : (r == 1 ? h1.q31 : h1.q30);    // Q[r-2][c-1]
+      const float Qc = r >= 1 ? q2[r - 1] : h2.q31;                        // Q[r-1][c-2]
+      const uint32_t Oa = r >= 1 ? o1[r - 1] : h1.o31;
+      const uint32_t Ob = r >= 2 ? o1[r - 2] : (r == 1 ? h1.o31 : h1.o30);
+      const uint32_t Oc = r >= 1 ? o2[r - 1] : h2.o31;
+      const bool hit = (e0 >> (r + 2)) & 1u;
+      float pa = Qa, pb = Qb, pc = Qc;
+      if (!EQG) {
+        const float x = Qa - gam((e1 >> (r + 1)) & 1u);  // gamma(C[r-1][c-1])
+        const float y = Qb - gam((e1 >> r) & 1u);        // gamma(C[r-2][c-1])
+        const float z = Qc - gam((e2 >> (r + 1)) & 1u);  // gamma(C[r-1][c-2])
+        pa = hit ? Qa : x;
+        pb = hit ? Qb : y;
+        pc = hit ? Qc : z;
+      }
+      float mx = pa;
+      uint32_t o = Oa;
+      if (pb > mx) {
+        mx = pb;
+        o = Ob;
+      }
+      if (pc > mx) {
+        mx = pc;
+        o = Oc;
+      }
+      float v = hit ? mx + 1.0f : fmaxf(EQG ? mx - g_open : mx, 0.0f);
+      const uint32_t key = kc + ((uint32_t)r << 16);
+      o = (hit && !(mx > 0.0f)) ? key : o;  // all predecessors 0: the path starts here
+      v = ((vmask >> r) & 1u) ? v : 0.0f;
+      if (v > cb) {
+        cb = v;
+        ck = key;
+        co = o;
+      }
+      // Pin the origin next to its score: the origins are first read in a later basic block
+      // (the next step's shuffles), so the compiler sinks their selects there and carries every
+      // compare mask (4 per cell, a scalar register pair each) across: 279 scalar spills at R = 16.
+      asm volatile("" : "+v"(o));
+      qn[r] = v;
+      on[r] = o;
+    }
+    if (cb > best || (cb == best && cb > 0.0f && ck < bkey)) {
+      best = cb;
+      bkey = ck;
+      borg = co;
+    }
+    DpAboveT out;
+    out.q30 = qn[R - 2];
+    out.q31 = qn[R - 1];
+    out.b = (w0 >> (R - 2)) & 3u;
+    out.o30 = on[R - 2];
+    out.o31 = on[R - 1];
+    h2 = h1;
+    h1 = h0;
+    w2 = w1;
+    w1 = w0;
+    return out;
+  }
+};
+
+// bnd: ceil(L / (64 R)) * ld TraceRec per pair (bnd_stride records between pairs); only read and
+// written by CRPs of more than one band. qmax_out may be NULL; seg_out: int32[4] (i0, j0, i1, j1) per pair.
+template <bool EQG, int R>
+__global__ __launch_bounds__(64) void k_crp_dp_trace(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
+                                                     const int2* __restrict__ dims, int row_lo, int row_hi, float go,
+                                                     float ge, TraceRec* __restrict__ bnd, int64_t bnd_stride,
+                                                     float* __restrict__ qmax_out, int32_t* __restrict__ seg_out) {
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int2 dm = dims[p];
+  const int Mp = dm.x, Np = dm.y;
+  if (!(Mp > row_lo && Mp <= row_hi)) return;  // the other R's launch takes this pair (wave-uniform)
+  constexpr int kBand = 64 * R;
+  const int nbands = (Mp + kBand - 1) / kBand;
+  DpLaneT<EQG, R> L;
+  L.go = go;
+  L.ge = ge;
+  L.Np = Np;
+  L.best = 0.0f;
+  L.bkey = L.borg = 0u;
+  for (int band = 0; band < nbands; ++band) {
+    const int row0 = band * kBand + lane * R;
+    const uint32_t* mrow = maskT + (size_t)p * mask_stride + (size_t)(row0 >> 5) * ld;
+    const int sh = row0 & 31;  // this lane's R rows inside its 32-row strip word
+    TraceRec* bout = bnd + (size_t)p * bnd_stride + (size_t)band * ld;
+    const TraceRec* bin = bnd + (size_t)p * bnd_stride + (size_t)(band - 1) * ld;
+    uint32_t rv = 0;
+    for (int r = 0; r < R; ++r) rv |= (uint32_t)((row0 + r >= 2) && (row0 + r < Mp)) << r;
+    L.rowvalid = rv;
+    L.key0 = (uint32_t)row0 << 16;
+    L.w1 = L.w2 = 0;
+    L.h1 = L.h2 = DpAboveT{0.0f, 0.0f, 0u, 0u, 0u};
+    float qa[R], qb[R], qc[R];
+    uint32_t oa[R], ob[R], oc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      qa[r] = qb[r] = qc[r] = 0.0f;
+      oa[r] = ob[r] = oc[r] = 0u;
+    }
+    DpAboveT pub{0.0f, 0.0f, 0u, 0u, 0u};
+    const int S_end = Np + 63;
+    const bool lane_active = row0 < Mp;
+    auto fetch = [&](int c) -> uint32_t {
+      if (!(lane_active && c >= 0 && c < Np)) return 0u;
+      return (mrow[c] >> sh) & ((1u << R) - 1u);
+    };
+    auto recv = [&](const DpAboveT& mine, int c) -> DpAboveT {
+      DpAboveT h;
+      h.q30 = __shfl_up(mine.q30, 1);
+      h.q31 = __shfl_up(mine.q31, 1);
+      h.b = (uint32_t)__shfl_up((int)mine.b, 1);
+      h.o30 = (uint32_t)__shfl_up((int)mine.o30, 1);
+      h.o31 = (uint32_t)__shfl_up((int)mine.o31, 1);
+      if (lane == 0) {
+        if (band > 0 && c >= 0 && c < Np) {
+          const float4 q = bin[c].q;
+          const uint4 o = bin[c].o;
+          h = DpAboveT{q.x, q.y, (uint32_t)q.z, o.x, o.y};
+        } else {
+          h = DpAboveT{0.0f, 0.0f, 0u, 0u, 0u};
+        }
+      }
+      return h;
+    };
+    auto publish = [&](const DpAboveT& o, int c) {
+      if (lane == 63 && band + 1 < nbands && c >= 0 && c < Np) {
+        bout[c].q = make_float4(o.q30, o.q31, (float)o.b, 0.0f);
+        bout[c].o = make_uint4(o.o30, o.o31, 0u, 0u);
+      }
+    };
+    uint32_t wnext = fetch(-lane);
+    for (int s = 0; s < S_end; s += 3) {
+      {
+        const int c = s - lane;
+        const uint32_t w0 = wnext;
+        wnext = fetch(c + 1);
+        const DpAboveT h0 = recv(pub, c);
+        pub = L.step(qa, oa, qb, ob, qc, oc, w0, h0, c);
+        publish(pub, c);
+      }
+      if (s + 1 < S_end) {
+        const int c = s + 1 - lane;
+        const uint32_t w0 = wnext;
+        wnext = fetch(c + 1);
+        const DpAboveT h0 = recv(pub, c);
+        pub = L.step(qc, oc, qa, oa, qb, ob, w0, h0, c);
+        publish(pub, c);
+      }
+      if (s + 2 < S_end) {
+        const int c = s + 2 - lane;
+        const uint32_t w0 = wnext;
+        wnext = fetch(c + 1);
+        const DpAboveT h0 = recv(pub, c);
+        pub = L.step(qb, ob, qc, oc, qa, oa, w0, h0, c);
+        publish(pub, c);
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  // wave reduction of (best, end key, origin) by the same rule as the per-cell update
+  float best = L.best;
+  uint32_t bkey = L.bkey, borg = L.borg;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v = __shfl_xor(best, o);
+    const uint32_t k = (uint32_t)__shfl_xor((int)bkey, o);
+    const uint32_t g = (uint32_t)__shfl_xor((int)borg, o);
+    if (v > best || (v == best && v > 0.0f && k < bkey)) {
+      best = v;
+      bkey = k;
+      borg = g;
+    }
+  }
+  if (lane == 0) {
+    if (qmax_out) qmax_out[p] = best;
+    const bool any = best > 0.0f;
+    int32_t* sg = seg_out + 4 * (size_t)p;
+    sg[0] = any ? (int)(borg >> 16) : -1;
+    sg[1] = any ? (int)(borg & 0xffffu) : -1;
+    sg[2] = any ? (int)(bkey >> 16) : -1;
+    sg[3] = any ? (int)(bkey & 0xffffu) : -1;
+  }
+}
+
 // Dense (M x N) uint8 CRP <-> strip words maskT[i/32][j] (bit i%32).
 __global__ void k_unpack_mask(const uint32_t* __restrict__ maskT, int ld, int M, int N, uint8_t* __restrict__ C) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1032,6 +1285,35 @@ void launch_dp(bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride, 
                        bstride, out);
   else
     launch_dp_r<ALIGN, 32>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s);
+}
+
+// The tracing DP (k_crp_dp_trace): R = 8 takes the CRPs of at most 512 rows, R = 16 the longer
+// ones; a batch whose longest CRP has more than 512 rows gets both launches and each wave keeps
+// the pairs of its own R. The exact-halves select (EQG) under the fast DP's condition only.
+constexpr int kTraceShortRows = 512;
+constexpr int kTraceMaxLen = 65535;  // 16 bits per coordinate of a packed cell
+
+inline int64_t trace_bnd_records(int L, int ld) {  // per pair: ceil(L / (64 R)) * ld
+  return L <= kTraceShortRows ? (int64_t)ld : (int64_t)((L + 64 * 16 - 1) / (64 * 16)) * ld;
+}
+
+template <int R>
+void launch_trace_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
+                    float go, float ge, TraceRec* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
+  const float k2 = 2.0f * go;
+  if (go == ge && k2 >= 0.0f && k2 <= 1024.0f && k2 == floorf(k2))
+    hipLaunchKernelGGL((k_crp_dp_trace<true, R>), dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, row_lo, row_hi, go,
+                       ge, bnd, bstride, qmax, seg);
+  else
+    hipLaunchKernelGGL((k_crp_dp_trace<false, R>), dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, row_lo, row_hi,
+                       go, ge, bnd, bstride, qmax, seg);
+}
+
+void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
+                  TraceRec* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
+  launch_trace_r<8>(nb, -1, kTraceShortRows, maskT, mstride, ld, dims, go, ge, bnd, bstride, qmax, seg, s);
+  if (L > kTraceShortRows)
+    launch_trace_r<16>(nb, kTraceShortRows, INT32_MAX, maskT, mstride, ld, dims, go, ge, bnd, bstride, qmax, seg, s);
 }
 
 // Per-track tables of one call, in workspace slot 0: prof (n_tracks x 12) | NX (n_tracks x ldn) |
@@ -1396,6 +1678,100 @@ extern "C" int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t
     launch_dp<0>(eqg, 1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, s);
   else
     launch_dp<1>(eqg, 1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, s);
+  ACOSS_LAUNCH_CHECK();
+  int h_err = 0;
+  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  if (h_err) {
+    set_error("CoverSongSimilarity: non-binary elements found in the input similarity matrix");
+    return ACOSS_E_NONBINARY;
+  }
+  return ACOSS_OK;
+}
+
+extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                                void* hip_stream) {
+  clear_error();
+  int rc = check_params(params);
+  if (rc) return rc;
+  if (n_pairs < 0 || n_tracks < 0 || max_len < 0) {
+    set_error("negative size");
+    return ACOSS_E_ARG;
+  }
+  if (n_pairs == 0) return ACOSS_OK;
+  if (!feats || !track_off || !track_len || !pairs || !seg_out) {
+    set_error("NULL input pointer or seg_out");
+    return ACOSS_E_ARG;
+  }
+  if (stacked_len(max_len, params->m, params->tau) > kTraceMaxLen) {
+    set_error("stacked length %d above %d: a packed cell has 16 bits per coordinate",
+              stacked_len(max_len, params->m, params->tau), kTraceMaxLen);
+    return ACOSS_E_SHAPE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  CrpPlan C;
+  if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, s, C))) return rc;
+  TrackPrep T;
+  prof_begin(PH_PREP, s);
+  if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, C.m, C.tau, s, &T))) return rc;
+  prof_end(PH_PREP, s);
+  // band-boundary records of the tracing DP, in a slot of their own (crp_plan's carving is the
+  // shipped DP's)
+  const int64_t tstride = trace_bnd_records(C.L, C.ld);
+  TraceRec* tb = static_cast<TraceRec*>(workspace(22, sizeof(TraceRec) * (size_t)tstride * (size_t)C.nb_alloc));
+  if (!tb) return ACOSS_E_HIP;
+
+  for (int64_t base = 0; base < n_pairs; base += C.nb_alloc) {
+    const int nb = (int)((n_pairs - base) < C.nb_alloc ? (n_pairs - base) : C.nb_alloc);
+    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
+    prof_begin(PH_DP_TRACE, s);
+    launch_trace(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, tb, tstride,
+                 qmax_out ? qmax_out + base : nullptr, seg_out + 4 * base, s);
+    ACOSS_LAUNCH_CHECK();
+    prof_end(PH_DP_TRACE, s);
+    if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
+  }
+  return ACOSS_OK;
+}
+
+extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                                float* score_out, int32_t* seg_out, void* hip_stream) {
+  clear_error();
+  if (M < 0 || N < 0 || !score_out || !seg_out) {
+    set_error("bad arguments to acoss_locate_crp");
+    return ACOSS_E_ARG;
+  }
+  if (M > kTraceMaxLen || N > kTraceMaxLen) {
+    set_error("matrix %d x %d above %d rows or columns: a packed cell has 16 bits per coordinate", M, N, kTraceMaxLen);
+    return ACOSS_E_SHAPE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if (M == 0 || N == 0) {
+    const float z = 0.0f;
+    const int32_t none[4] = {-1, -1, -1, -1};
+    ACOSS_HIP_CHECK(hipMemcpyAsync(score_out, &z, 4, hipMemcpyHostToDevice, s));
+    ACOSS_HIP_CHECK(hipMemcpyAsync(seg_out, none, sizeof(none), hipMemcpyHostToDevice, s));
+    ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+    return ACOSS_OK;
+  }
+  const int ld = (int)align_up((size_t)N, 8);
+  const int nstrips = (M + 31) / 32;
+  const int64_t trecs = trace_bnd_records(M, ld);
+  const size_t mask_bytes = align_up(4 * (size_t)nstrips * ld, 256);
+  char* ws = static_cast<char*>(workspace(23, 256 + mask_bytes + sizeof(TraceRec) * (size_t)trecs));
+  if (!ws) return ACOSS_E_HIP;
+  int* d_err = reinterpret_cast<int*>(ws);
+  int2* d_dims = reinterpret_cast<int2*>(ws + 64);
+  uint32_t* maskT = reinterpret_cast<uint32_t*>(ws + 256);
+  TraceRec* bnd = reinterpret_cast<TraceRec*>(ws + 256 + mask_bytes);
+  const int h_hdr[4] = {0, 0, M, N};  // err, pad, dims
+  ACOSS_HIP_CHECK(hipMemcpy(d_err, h_hdr, 8, hipMemcpyHostToDevice));
+  ACOSS_HIP_CHECK(hipMemcpy(d_dims, h_hdr + 2, 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, maskT, d_err);
+  ACOSS_LAUNCH_CHECK();
+  launch_trace(1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, seg_out, s);
   ACOSS_LAUNCH_CHECK();
   int h_err = 0;
   ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));

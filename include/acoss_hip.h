@@ -88,6 +88,25 @@ int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t N, const a
 int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t align, float gamma_open, float gamma_ext,
                     float* score_out, void* hip_stream);
 
+/* Where the Qmax alignment lies (no counterpart call in the reference, whose CoverSongSimilarity
+ * returns the whole score matrix instead): acoss_crp_align's Qmax of every pair together with
+ * the first cell, in row-major order, that holds it (i1, j1) and the cell its path began at
+ * (i0, j0), by origin propagation inside the DP (crp.hip k_crp_dp_trace); no M' x N' score matrix
+ * is written. A path extends through the predecessors (i-1, j-1), (i-2, j-1), (i-1, j-2) in that
+ * order, the first one attaining the maximum wins; a hit whose predecessors are all 0 starts one.
+ * serra09 only. seg_out: int32[4 n_pairs] = (i0, j0, i1, j1) in stacked-frame rows (query) and
+ * columns (reference); qmax_out, oti_out may be NULL; seg_out must not be. A pair whose Qmax is 0
+ * gets (-1, -1, -1, -1). The CRP is the one acoss_crp_align computes (same kernels, same
+ * workspace), qmax_out is its qmax_out bit for bit. A stacked length above 65,535 returns
+ * ACOSS_E_SHAPE (a cell is packed into 16 + 16 bits). */
+int acoss_crp_locate(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                     int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                     float* qmax_out, int32_t* seg_out, int32_t* oti_out, void* hip_stream);
+/* the same on a given binary matrix (mirrors acoss_align_crp, non-binary input refused alike):
+ * score_out float[1], seg_out int32[4]; M or N above 65,535 returns ACOSS_E_SHAPE. */
+int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                     float* score_out, int32_t* seg_out, void* hip_stream);
+
 /* acoss smith_waterman_constrained (A8, acoss/algorithms/utils/alignment_tools.py:25-46) on
  * a batch of binary matrices: matrix b is (rows[b] x cols[b]) uint8 at byte offset off[b]
  * of `mats`. score_out: double[n_mats]. Bit-exact float64 (same evaluation order). */
