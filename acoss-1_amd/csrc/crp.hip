@@ -22,11 +22,8 @@
 //    later evaluated in the squared domain (sq_threshold), so no per-cell sqrt is needed.
 //  * k_crp_panel: recomputes the distances of a 32-row x 256-column panel and writes the
 //    CRP as one 32-bit word per (32-row strip, column): the layout the DP consumes.
-//  * k_crp_dp: one wave per pair. Lane l owns 32 rows of a 2048-row band and sweeps the
-//    columns skewed by one column per lane (anti-diagonal wavefront); the two boundary rows
-//    pass down one lane per step with __shfl_up; bands chain through a small HBM buffer.
-//  * k_crp_dp_trace: the serra09 DP again, every cell also carrying the cell where its path
-//    began, for acoss_crp_locate / acoss_locate_crp (where the Qmax alignment starts and ends).
+// The wavefront DP over those words (k_crp_dp*, and k_crp_dp_trace for acoss_crp_locate /
+// acoss_locate_crp) is crp_dp.hip; this file reaches it through launch_dp and launch_trace.
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -451,733 +448,6 @@ __global__ __launch_bounds__(256) void k_crp_panel(CrpBatch B, const float* __re
   }
 }
 
-// --------------------------------------------------------------------------------------
-// k_crp_dp<ALIGN, EQG, R>: essentia CoverSongSimilarity(serra09 | chen17, 'symmetric').
-// One wave per pair; lane l owns R rows, band*64R + Rl .. +R-1 (R = 32, 16 or 8 by the batch's
-// longest CRP, so short tracks keep every lane busy); column c = s - l at step s.
-// --------------------------------------------------------------------------------------
-struct DpAbove {  // what lane l-1 (or the band above) hands down for one column
-  float q30, q31;  // its last two rows (R-2, R-1)
-  uint32_t b;      // bit0 = C[row R-2], bit1 = C[row R-1]
-};
-
-// FAST (serra09 with gamma_open == gamma_ext = K/2 >= 0, the reference's setting): every score is
-// an exact multiple of 1/2, so "hit ? mx + 1 : max(mx - go, 0)" is max(fma(hit, 1 + go, mx - go), 0)
-// exactly, and the validity masks move out of the row loop: the kernel zeroes the CRP words of
-// columns < 2 and rows outside [2, Mp) at the fetch. Cells there then hold 0 (top-left: all their
-// predecessors are 0) or at most max(0, best - go) (bottom/right: no hit, and they never feed a
-// valid cell), so neither the valid scores nor their maximum change.
-// v_cvt_f32_ubyteB: byte B of v as a float (the compiler emits only the byte-0 form plus shifts).
-template <int B>
-__device__ __forceinline__ float cvt_f32_ubyte(uint32_t v) {
-  float f;
-  if constexpr (B == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(f) : "v"(v));
-  else if constexpr (B == 1) asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(f) : "v"(v));
-  else if constexpr (B == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(f) : "v"(v));
-  else asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(f) : "v"(v));
-  return f;
-}
-
-// b is a constant after the row loops unroll, so the switch folds away
-__device__ __forceinline__ float cvt_f32_ubyte_n(uint32_t v, int b) {
-  switch (b) {
-    case 0: return cvt_f32_ubyte<0>(v);
-    case 1: return cvt_f32_ubyte<1>(v);
-    case 2: return cvt_f32_ubyte<2>(v);
-    default: return cvt_f32_ubyte<3>(v);
-  }
-}
-
-template <int ALIGN, bool EQG, int R, bool FAST = false>
-struct DpLane {
-  float go, ge;
-  int Np, lane, c_off;  // column of this lane at step s: s - lane
-  uint32_t rowvalid;    // bit r: 2 <= global row < Mp
-  uint32_t w1, w2;      // CRP words of columns c-1, c-2 (bit r = row r)
-  DpAbove h1, h2;       // from above for columns c-1, c-2
-  float best;
-
-  __device__ __forceinline__ float gam(uint32_t bit) const { return EQG ? go : (bit ? go : ge); }
-
-  // qn: new column c; q1: column c-1; q2: column c-2. w0: CRP word of column c;
-  // h0: from above for column c. Returns the values to hand to the lane below.
-  __device__ __forceinline__ DpAbove step(float (&qn)[R], const float (&q1)[R], const float (&q2)[R],
-                                          uint32_t w0, const DpAbove& h0, int c) {
-    const bool colvalid = (c >= 2) && (c < Np);
-    const uint32_t vmask = colvalid ? rowvalid : 0u;
-    // extended words: bit r+2 <-> row r; bits 0,1 <-> rows -2,-1 (from above)
-    const uint64_t e0 = ((uint64_t)w0 << 2) | h0.b;
-    const uint64_t e1 = ((uint64_t)w1 << 2) | h1.b;
-    const uint64_t e2 = ((uint64_t)w2 << 2) | h2.b;
-    if constexpr (FAST) {
-      // two rows per v_pk_add_f32 / v_pk_fma_f32; the hit bits as bytes (rows k, k+8, k+16, k+24
-      // of one masked word), one v_cvt_f32_ubyteN each
-      typedef float dp_f32x2 __attribute__((ext_vector_type(2)));
-      const dp_f32x2 g1 = {1.0f + go, 1.0f + go};
-      const dp_f32x2 ngo = {-go, -go};
-      uint32_t bm[R < 8 ? R : 8];
-#pragma unroll
-      for (int k = 0; k < (R < 8 ? R : 8); ++k) bm[k] = (w0 >> k) & 0x01010101u;
-#pragma unroll
-      for (int r = 0; r < R; r += 2) {
-        float mxs[2], hb[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int rr = r + e;
-          const float Qa = rr >= 1 ? q1[rr - 1] : h1.q31;
-          const float Qb = rr >= 2 ? q1[rr - 2] : (rr == 1 ? h1.q31 : h1.q30);
-          const float Qc = rr >= 1 ? q2[rr - 1] : h2.q31;
-          mxs[e] = fmaxf(fmaxf(Qa, Qb), Qc);
-          hb[e] = cvt_f32_ubyte_n(bm[rr & 7], rr >> 3);
-        }
-        const dp_f32x2 mx = {mxs[0], mxs[1]};
-        const dp_f32x2 hv = {hb[0], hb[1]};
-        const dp_f32x2 t = __builtin_elementwise_fma(hv, g1, mx + ngo);
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(best), "v"(t.x), "v"(t.y));
-        qn[r] = fmaxf(t.x, 0.0f);
-        qn[r + 1] = fmaxf(t.y, 0.0f);
-      }
-    } else {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float Qa = r >= 1 ? q1[r - 1] : h1.q31;                            // Q[r-1][c-1]
-      float Qb = r >= 2 ? q1[r - 2] : (r == 1 ? h1.q31 : h1.q30);              // Q[r-2][c-1]
-      float Qc = r >= 1 ? q2[r - 1] : h2.q31;                                  // Q[r-1][c-2]
-      if (ALIGN == 1) {
-        Qb = Qb + (float)((e0 >> (r + 1)) & 1u);  // + C[r-1][c]
-        Qc = Qc + (float)((e1 >> (r + 2)) & 1u);  // + C[r][c-1]
-      }
-      const bool hit = (e0 >> (r + 2)) & 1u;
-      float v;
-      if (EQG) {
-        const float mx = fmaxf(fmaxf(Qa, Qb), Qc);
-        v = hit ? mx + 1.0f : fmaxf(mx - go, 0.0f);
-      } else {
-        const float x = Qa - gam((e1 >> (r + 1)) & 1u);  // gamma(C[r-1][c-1])
-        const float y = Qb - gam((e1 >> r) & 1u);        // gamma(C[r-2][c-1])
-        const float z = Qc - gam((e2 >> (r + 1)) & 1u);  // gamma(C[r-1][c-2])
-        const float miss = fmaxf(fmaxf(0.0f, x), fmaxf(y, z));
-        v = hit ? fmaxf(fmaxf(Qa, Qb), Qc) + 1.0f : miss;
-      }
-      v = ((vmask >> r) & 1u) ? v : 0.0f;
-      best = fmaxf(best, v);
-      qn[r] = v;
-    }
-    }
-    DpAbove out;
-    out.q30 = qn[R - 2];
-    out.q31 = qn[R - 1];
-    out.b = (w0 >> (R - 2)) & 3u;
-    h2 = h1;
-    h1 = h0;
-    w2 = w1;
-    w1 = w0;
-    return out;
-  }
-};
-
-template <int ALIGN, bool EQG, int R, bool FAST>
-__device__ __forceinline__ void crp_dp_body(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
-                                               const int2* __restrict__ dims, float go, float ge,
-                                               float4* __restrict__ bnd, int64_t bnd_stride,
-                                               float* __restrict__ out) {
-  const int p = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int2 dm = dims[p];
-  const int Mp = dm.x, Np = dm.y;
-  float best = 0.0f;
-  constexpr int kBand = 64 * R;
-  const int nbands = (Mp + kBand - 1) / kBand;
-  for (int band = 0; band < nbands; ++band) {
-    const int row0 = band * kBand + lane * R;
-    const uint32_t* mrow = maskT + (size_t)p * mask_stride + (size_t)(row0 >> 5) * ld;
-    const int sh = row0 & 31;  // this lane's R rows inside its 32-row strip word
-    float4* bout = bnd + (size_t)p * bnd_stride + (size_t)band * ld;
-    const float4* bin = bnd + (size_t)p * bnd_stride + (size_t)(band - 1) * ld;
-    DpLane<ALIGN, EQG, R, FAST> L;
-    L.go = go;
-    L.ge = ge;
-    L.Np = Np;
-    L.lane = lane;
-    uint32_t rv = 0;
-    for (int r = 0; r < R; ++r) rv |= (uint32_t)((row0 + r >= 2) && (row0 + r < Mp)) << r;
-    L.rowvalid = rv;
-    L.w1 = L.w2 = 0;
-    L.h1 = L.h2 = DpAbove{0.0f, 0.0f, 0u};
-    L.best = 0.0f;
-    float qa[R], qb[R], qc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) qa[r] = qb[r] = qc[r] = 0.0f;
-    DpAbove pub{0.0f, 0.0f, 0u};
-    const int S_end = Np + 63;
-    const bool lane_active = row0 < Mp;
-    auto fetch = [&](int c) -> uint32_t {
-      if (!(lane_active && c >= (FAST ? 2 : 0) && c < Np)) return 0u;
-      const uint32_t w = mrow[c];
-      const uint32_t wr = R == 32 ? w : (w >> sh) & ((1u << (R & 31)) - 1u);
-      return FAST ? (wr & rv) : wr;
-    };
-    auto recv = [&](const DpAbove& mine, int c) -> DpAbove {
-      DpAbove h;
-      h.q30 = __shfl_up(mine.q30, 1);
-      h.q31 = __shfl_up(mine.q31, 1);
-      h.b = (uint32_t)__shfl_up((int)mine.b, 1);
-      if (lane == 0) {
-        if (band > 0 && c >= 0 && c < Np) {
-          const float4 v = bin[c];
-          h = DpAbove{v.x, v.y, (uint32_t)v.z};
-        } else {
-          h = DpAbove{0.0f, 0.0f, 0u};
-        }
-      }
-      return h;
-    };
-    auto publish = [&](const DpAbove& o, int c) {
-      if (lane == 63 && band + 1 < nbands && c >= 0 && c < Np) bout[c] = make_float4(o.q30, o.q31, (float)o.b, 0.0f);
-    };
-    uint32_t wnext = fetch(-lane);
-    for (int s = 0; s < S_end; s += 3) {
-      {
-        const int c = s - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAbove h0 = recv(pub, c);
-        pub = L.step(qa, qb, qc, w0, h0, c);
-        publish(pub, c);
-      }
-      if (s + 1 < S_end) {
-        const int c = s + 1 - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAbove h0 = recv(pub, c);
-        pub = L.step(qc, qa, qb, w0, h0, c);
-        publish(pub, c);
-      }
-      if (s + 2 < S_end) {
-        const int c = s + 2 - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAbove h0 = recv(pub, c);
-        pub = L.step(qb, qc, qa, w0, h0, c);
-        publish(pub, c);
-      }
-    }
-    best = fmaxf(best, L.best);
-    __threadfence_block();
-    __syncthreads();
-  }
-  best = wave_max(best);
-  if (lane == 0) out[p] = best;
-}
-
-template <int ALIGN, bool EQG, int R>
-__global__ __launch_bounds__(64) void k_crp_dp(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
-                                               const int2* __restrict__ dims, float go, float ge,
-                                               float4* __restrict__ bnd, int64_t bnd_stride,
-                                               float* __restrict__ out) {
-  crp_dp_body<ALIGN, EQG, R, false>(maskT, mask_stride, ld, dims, go, ge, bnd, bnd_stride, out);
-}
-
-// No occupancy hint: the FAST body compiles to about 200 VGPRs (2 waves per SIMD), which measured
-// faster than forcing it into 128 (4 waves per SIMD): 14.2 vs 14.8 ms per covers80 step.
-template <int R>
-__global__ __launch_bounds__(64) void k_crp_dp_fast(
-    const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld, const int2* __restrict__ dims, float go, float ge,
-    float4* __restrict__ bnd, int64_t bnd_stride, float* __restrict__ out) {
-  crp_dp_body<0, true, R, true>(maskT, mask_stride, ld, dims, go, ge, bnd, bnd_stride, out);
-}
-
-// --------------------------------------------------------------------------------------
-// k_crp_dp_grp: the FAST DP (serra09, gamma_open == gamma_ext = K/2) with SEVERAL pairs per
-// wave for CRPs of at most 2048 rows: a group of LP = ceil(L / 32) lanes per pair (lane ll owns
-// rows 32 ll .. 32 ll + 31, one band), G = 64 / LP groups per wave. A one-pair wave walks
-// N' + 63 steps however short the pair; a group walks N' + LP - 1, and every lane keeps 32 rows
-// per step, so short tracks (Da-TACOS lengths: L ~ 500) no longer leave most lanes idle or pay
-// the per-step shuffles for 8 rows. Same recurrence, same DpLane step: bit-identical scores.
-// --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_crp_dp_grp(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
-                                                   const int2* __restrict__ dims, int nb, int LP, float go,
-                                                   float* __restrict__ out) {
-  constexpr int R = 32;
-  __shared__ float s_best[64];
-  const int lane = threadIdx.x;
-  const int G = 64 / LP;
-  const int g = lane / LP, ll = lane - g * LP;
-  const int p = blockIdx.x * G + g;
-  const bool in_group = g < G && p < nb;
-  const int2 dm = in_group ? dims[p] : make_int2(0, 0);
-  const int Mp = dm.x, Np = dm.y;
-  const int row0 = ll * R;
-  const uint32_t* mrow = maskT + (size_t)(in_group ? p : 0) * mask_stride + (size_t)ll * ld;
-  DpLane<0, true, R, true> L;
-  L.go = go;
-  L.ge = go;
-  L.Np = Np;
-  L.lane = ll;
-  uint32_t rv = 0;
-  for (int r = 0; r < R; ++r) rv |= (uint32_t)((row0 + r >= 2) && (row0 + r < Mp)) << r;
-  L.rowvalid = rv;
-  L.w1 = L.w2 = 0;
-  L.h1 = L.h2 = DpAbove{0.0f, 0.0f, 0u};
-  L.best = 0.0f;
-  float qa[R], qb[R], qc[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) qa[r] = qb[r] = qc[r] = 0.0f;
-  DpAbove pub{0.0f, 0.0f, 0u};
-  // steps until every group of the wave is done (wave-uniform bound)
-  const int S_end = (int)wave_max_u32(in_group ? (unsigned)(Np + LP - 1) : 0u);
-  const bool lane_active = in_group && row0 < Mp;
-  auto fetch = [&](int c) -> uint32_t {
-    if (!(lane_active && c >= 2 && c < Np)) return 0u;
-    return mrow[c] & rv;
-  };
-  auto recv = [&](const DpAbove& mine) -> DpAbove {
-    DpAbove h;
-    h.q30 = __shfl_up(mine.q30, 1);
-    h.q31 = __shfl_up(mine.q31, 1);
-    h.b = (uint32_t)__shfl_up((int)mine.b, 1);
-    if (ll == 0) h = DpAbove{0.0f, 0.0f, 0u};  // the group's first rows: nothing above
-    return h;
-  };
-  uint32_t wnext = fetch(-ll);
-  for (int s = 0; s < S_end; s += 3) {
-    {
-      const int c = s - ll;
-      const uint32_t w0 = wnext;
-      wnext = fetch(c + 1);
-      pub = L.step(qa, qb, qc, w0, recv(pub), c);
-    }
-    if (s + 1 < S_end) {
-      const int c = s + 1 - ll;
-      const uint32_t w0 = wnext;
-      wnext = fetch(c + 1);
-      pub = L.step(qc, qa, qb, w0, recv(pub), c);
-    }
-    if (s + 2 < S_end) {
-      const int c = s + 2 - ll;
-      const uint32_t w0 = wnext;
-      wnext = fetch(c + 1);
-      pub = L.step(qb, qc, qa, w0, recv(pub), c);
-    }
-  }
-  // per-group maximum through LDS (groups need not be a power of two wide)
-  s_best[lane] = L.best;
-  __syncthreads();
-  if (in_group && ll == 0) {
-    float b = 0.0f;
-    for (int k = 0; k < LP; ++k) b = fmaxf(b, s_best[lane + k]);
-    out[p] = b;
-  }
-}
-
-// --------------------------------------------------------------------------------------
-// k_crp_dp_pk<ALIGN>: k_crp_dp<ALIGN, true, 32> in packed 16-bit integers. With
-// gamma_open == gamma_ext = K/2 (K a small integer, 1 for the reference's 0.5), every score is
-// a multiple of 1/2, so 2Q is an exact integer below 4 L: lane l keeps rows (h, h + 16) of a
-// column in one u32 (row h low, row h + 16 high) and takes two rows per v_pk_max_u16 /
-// v_pk_add_u16 / saturating v_pk_sub_u16 (max(x - K, 0) in one instruction). The predecessor
-// rows of pair h are pair h - 1 / h - 2 of the previous columns; pairs 0 and 1 splice in the
-// rows handed down by the lane above (v_perm). Bit-identical to the f32 kernel: both compute
-// the same exact multiples of 1/2 (the f32 values never round).
-// --------------------------------------------------------------------------------------
-typedef unsigned short dp_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk16(dp_u16x2 v) { return __builtin_bit_cast(unsigned, v); }
-__device__ __forceinline__ dp_u16x2 up16(unsigned v) { return __builtin_bit_cast(dp_u16x2, v); }
-__device__ __forceinline__ unsigned pk_max16(unsigned a, unsigned b) { return pk16(__builtin_elementwise_max(up16(a), up16(b))); }
-__device__ __forceinline__ unsigned pk_add16(unsigned a, unsigned b) { return pk16(up16(a) + up16(b)); }
-__device__ __forceinline__ unsigned pk_sub16(unsigned a, unsigned b) { return pk16(up16(a) - up16(b)); }
-__device__ __forceinline__ unsigned pk_subsat16(unsigned a, unsigned b) {
-  return pk16(__builtin_elementwise_sub_sat(up16(a), up16(b)));
-}
-
-struct DpAbovePk {  // what lane l-1 (or the band above) hands down for one column
-  unsigned hq;      // its rows 30 (low half) and 31 (high half), x2 units
-  uint32_t b;       // bit0 = C[row 30], bit1 = C[row 31]
-};
-
-template <int ALIGN>
-struct DpLanePk {
-  unsigned K;          // gamma in x2 units, both halves
-  int Np;
-  uint32_t rz0, rz1;   // AND masks of pairs 0 / 1: rows 0 and 1 of the first band are 0
-  uint32_t w1, w2;     // CRP words of columns c-1, c-2
-  DpAbovePk h1, h2;    // from above for columns c-1, c-2
-  unsigned best;
-
-  __device__ __forceinline__ DpAbovePk step(unsigned (&pn)[16], const unsigned (&p1)[16], const unsigned (&p2)[16],
-                                            uint32_t w0, const DpAbovePk& h0, int c) {
-    const bool colok = (c >= 2) && (c < Np);
-    // rows (-1, 15) and (-2, 14) of column c-1, (-1, 15) of column c-2
-    const unsigned a0 = __builtin_amdgcn_perm(p1[15], h1.hq, 0x05040302u);
-    const unsigned b0 = __builtin_amdgcn_perm(p1[14], h1.hq, 0x05040100u);
-    const unsigned c0 = __builtin_amdgcn_perm(p2[15], h2.hq, 0x05040302u);
-#pragma unroll
-    for (int h = 0; h < 16; ++h) {
-      const unsigned A = h >= 1 ? p1[h - 1] : a0;                  // Q[r-1][c-1]
-      unsigned B = h >= 2 ? p1[h - 2] : (h == 1 ? a0 : b0);        // Q[r-2][c-1]
-      unsigned Cq = h >= 1 ? p2[h - 1] : c0;                       // Q[r-1][c-2]
-      if (ALIGN == 1) {
-        const unsigned cb = h >= 1 ? (w0 >> (h - 1)) & 0x10001u : ((h0.b >> 1) & 1u) | (((w0 >> 15) & 1u) << 16);
-        B = pk_add16(B, cb << 1);                                  // + C[r-1][c]
-        Cq = pk_add16(Cq, ((w1 >> h) & 0x10001u) << 1);            // + C[r][c-1]
-      }
-      const unsigned mx = pk_max16(pk_max16(A, B), Cq);
-      const unsigned m = pk_sub16(0u, (w0 >> h) & 0x10001u);      // 0xffff where C[r][c] = 1
-      unsigned v = (m & pk_add16(mx, 0x00020002u)) | (~m & pk_subsat16(mx, K));
-      if (h == 0) v &= rz0;
-      if (h == 1) v &= rz1;
-      v = colok ? v : 0u;
-      best = pk_max16(best, v);
-      pn[h] = v;
-    }
-    DpAbovePk out;
-    out.hq = __builtin_amdgcn_perm(pn[15], pn[14], 0x07060302u);
-    out.b = (w0 >> 30) & 3u;
-    h2 = h1;
-    h1 = h0;
-    w2 = w1;
-    w1 = w0;
-    return out;
-  }
-};
-
-template <int ALIGN>
-__global__ __launch_bounds__(64) void k_crp_dp_pk(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
-                                                  const int2* __restrict__ dims, unsigned K,
-                                                  float4* __restrict__ bnd, int64_t bnd_stride,
-                                                  float* __restrict__ out) {
-  const int p = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int2 dm = dims[p];
-  const int Mp = dm.x, Np = dm.y;
-  unsigned best = 0u;
-  constexpr int kBand = 64 * 32;
-  const int nbands = (Mp + kBand - 1) / kBand;
-  for (int band = 0; band < nbands; ++band) {
-    const int row0 = band * kBand + lane * 32;
-    const uint32_t* mrow = maskT + (size_t)p * mask_stride + (size_t)(row0 >> 5) * ld;
-    float4* bout = bnd + (size_t)p * bnd_stride + (size_t)band * ld;
-    const float4* bin = bnd + (size_t)p * bnd_stride + (size_t)(band - 1) * ld;
-    DpLanePk<ALIGN> L;
-    L.K = K * 0x10001u;
-    L.Np = Np;
-    L.rz0 = row0 == 0 ? 0xffff0000u : 0xffffffffu;
-    L.rz1 = L.rz0;
-    L.w1 = L.w2 = 0;
-    L.h1 = L.h2 = DpAbovePk{0u, 0u};
-    L.best = 0u;
-    unsigned qa[16], qb[16], qc[16];
-#pragma unroll
-    for (int h = 0; h < 16; ++h) qa[h] = qb[h] = qc[h] = 0u;
-    DpAbovePk pub{0u, 0u};
-    const int S_end = Np + 63;
-    const bool lane_active = row0 < Mp;
-    auto fetch = [&](int c) -> uint32_t { return (lane_active && c >= 0 && c < Np) ? mrow[c] : 0u; };
-    auto recv = [&](const DpAbovePk& mine, int c) -> DpAbovePk {
-      DpAbovePk h;
-      h.hq = (unsigned)__shfl_up((int)mine.hq, 1);
-      h.b = (uint32_t)__shfl_up((int)mine.b, 1);
-      if (lane == 0) {
-        if (band > 0 && c >= 0 && c < Np) {
-          const float4 v = bin[c];
-          h = DpAbovePk{__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y)};
-        } else {
-          h = DpAbovePk{0u, 0u};
-        }
-      }
-      return h;
-    };
-    auto publish = [&](const DpAbovePk& o, int c) {
-      if (lane == 63 && band + 1 < nbands && c >= 0 && c < Np)
-        bout[c] = make_float4(__builtin_bit_cast(float, o.hq), __builtin_bit_cast(float, o.b), 0.0f, 0.0f);
-    };
-    uint32_t wnext = fetch(-lane);
-    for (int s = 0; s < S_end; s += 3) {
-      {
-        const int c = s - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAbovePk h0 = recv(pub, c);
-        pub = L.step(qa, qb, qc, w0, h0, c);
-        publish(pub, c);
-      }
-      if (s + 1 < S_end) {
-        const int c = s + 1 - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAbovePk h0 = recv(pub, c);
-        pub = L.step(qc, qa, qb, w0, h0, c);
-        publish(pub, c);
-      }
-      if (s + 2 < S_end) {
-        const int c = s + 2 - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAbovePk h0 = recv(pub, c);
-        pub = L.step(qb, qc, qa, w0, h0, c);
-        publish(pub, c);
-      }
-    }
-    best = pk_max16(best, L.best);
-    __threadfence_block();
-    __syncthreads();
-  }
-  const unsigned b2 = max(best & 0xffffu, best >> 16);
-  const float r = wave_max(0.5f * (float)b2);
-  if (lane == 0) out[p] = r;
-}
-
-// --------------------------------------------------------------------------------------
-// k_crp_dp_trace<EQG, R>: the serra09 DP of k_crp_dp<0, ., R> with ORIGIN PROPAGATION: every
-// cell carries, beside its score, the packed cell (i0 << 16) | j0 where its path began, and the
-// wave reduces (Qmax, end cell, origin of the end cell) instead of a bare maximum. Memory per
-// pair stays O(1) beyond the DP's own: no M' x N' score matrix is written.
-//  * predecessors in the fixed order a = (i-1, j-1), b = (i-2, j-1), c = (i-1, j-2); the origin is
-//    that of the FIRST predecessor attaining the maximum (raw values on a hit, penalised values
-//    on a miss; a strictly greater value replaces, an equal one does not); a hit whose
-//    predecessors are all 0 starts a path at itself.
-//  * the end cell is the first cell in row-major order holding Qmax. The skewed walk does not
-//    visit cells in row-major order, so every update compares the packed end key (i << 16) | j:
-//    v > best || (v == best && v > 0 && key < bestkey). Inside one step a lane's cells share a
-//    column and come in ascending rows, so there "first wins" is the strict compare alone.
-//  * general arithmetic, validity per cell (any gamma). EQG = true is launched only where
-//    gamma_open == gamma_ext = K/2 (K a small non-negative integer): every score is then an exact
-//    multiple of 1/2, x - gamma never rounds, and the first maximum of the penalised values is the
-//    first maximum of the raw ones, so one select serves hit and miss. Origins are defined where
-//    a path can only begin on a hit, i.e. for gamma >= 0.
-//  * R = 8 rows per lane for CRPs of at most 512 rows, R = 16 above (bands of 64 R rows): three
-//    rotating columns of R scores and R origins are 6 R live registers. A launch takes the pairs
-//    with row_lo < M' <= row_hi and leaves the others to the launch of the other R.
-//  * the values handed to the next lane, and across a band boundary through HBM, are the last two
-//    rows' scores, CRP bits and origins (TraceRec).
-// Every lane runs every step and selects; the only branches around a shuffle are wave-uniform.
-// --------------------------------------------------------------------------------------
-struct DpAboveT {   // what lane l-1 (or the band above) hands down for one column
-  float q30, q31;   // scores of its last two rows (R-2, R-1)
-  uint32_t b;       // bit0 = C[row R-2], bit1 = C[row R-1]
-  uint32_t o30, o31;  // origins of the same two cells
-};
-
-struct TraceRec {  // one column of a band boundary, 32 B
-  float4 q;        // q30, q31, bits as float, unused
-  uint4 o;         // o30, o31, unused
-};
-
-template <bool EQG, int R>
-struct DpLaneT {
-  static_assert(R <= 16, "the extended CRP words are 32-bit");
-  float go, ge;
-  int Np;
-  uint32_t rowvalid;  // bit r: 2 <= global row < Mp
-  uint32_t key0;      // (global row of this lane's row 0) << 16
-  uint32_t w1, w2;    // CRP words of columns c-1, c-2 (bit r = row r)
-  DpAboveT h1, h2;    // from above for columns c-1, c-2
-  float best;         // this lane's maximum so far, its end key and the origin of that cell
-  uint32_t bkey, borg;
-
-  // (qn, on): new column c; (q1, o1): column c-1; (q2, o2): column c-2.
-  __device__ __forceinline__ DpAboveT step(float (&qn)[R], uint32_t (&on)[R], const float (&q1)[R],
-                                           const uint32_t (&o1)[R], const float (&q2)[R], const uint32_t (&o2)[R],
-                                           uint32_t w0, const DpAboveT& h0, int c) {
-    const bool colvalid = (c >= 2) && (c < Np);
-    const uint32_t vmask = colvalid ? rowvalid : 0u;
-    // extended words: bit r+2 <-> row r; bits 0,1 <-> rows -2,-1 (from above)
-    const uint32_t e0 = (w0 << 2) | h0.b;
-    const uint32_t e1 = (w1 << 2) | h1.b;
-    const uint32_t e2 = (w2 << 2) | h2.b;
-    const uint32_t kc = key0 + (uint32_t)c;  // key of (row 0, c); only used where colvalid
-    const float g_open = go, g_ext = ge;     // by value: a select between members is a select of addresses
-    auto gam = [&](uint32_t bit) { return bit ? g_open : g_ext; };
-    float cb = 0.0f;                         // this column's first maximum, its key and origin
-    uint32_t ck = 0u, co = 0u;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float Qa = r >= 1 ? q1[r - 1] : h1.q31;                        // Q[r-1][c-1]
-      const float Qb = r >= 2 ? q1[r - 2] : (r == 1 ? h1.q31 : h1.q30);    // Q[r-2][c-1]
-      const float Qc = r >= 1 ? q2[r - 1] : h2.q31;                        // Q[r-1][c-2]
-      const uint32_t Oa = r >= 1 ? o1[r - 1] : h1.o31;
-      const uint32_t Ob = r >= 2 ? o1[r - 2] : (r == 1 ? h1.o31 : h1.o30);
-      const uint32_t Oc = r >= 1 ? o2[r - 1] : h2.o31;
-      const bool hit = (e0 >> (r + 2)) & 1u;
-      float pa = Qa, pb = Qb, pc = Qc;
-      if (!EQG) {
-        const float x = Qa - gam((e1 >> (r + 1)) & 1u);  // gamma(C[r-1][c-1])
-        const float y = Qb - gam((e1 >> r) & 1u);        // gamma(C[r-2][c-1])
-        const float z = Qc - gam((e2 >> (r + 1)) & 1u);  // gamma(C[r-1][c-2])
-        pa = hit ? Qa : x;
-        pb = hit ? Qb : y;
-        pc = hit ? Qc : z;
-      }
-      float mx = pa;
-      uint32_t o = Oa;
-      if (pb > mx) {
-        mx = pb;
-        o = Ob;
-      }
-      if (pc > mx) {
-        mx = pc;
-        o = Oc;
-      }
-      float v = hit ? mx + 1.0f : fmaxf(EQG ? mx - g_open : mx, 0.0f);
-      const uint32_t key = kc + ((uint32_t)r << 16);
-      o = (hit && !(mx > 0.0f)) ? key : o;  // all predecessors 0: the path starts here
-      v = ((vmask >> r) & 1u) ? v : 0.0f;
-      if (v > cb) {
-        cb = v;
-        ck = key;
-        co = o;
-      }
-      // Pin the origin next to its score: the origins are first read in a later basic block
-      // (the next step's shuffles), so the compiler sinks their selects there and carries every
-      // compare mask (4 per cell, a scalar register pair each) across: 279 scalar spills at R = 16.
-      asm volatile("" : "+v"(o));
-      qn[r] = v;
-      on[r] = o;
-    }
-    if (cb > best || (cb == best && cb > 0.0f && ck < bkey)) {
-      best = cb;
-      bkey = ck;
-      borg = co;
-    }
-    DpAboveT out;
-    out.q30 = qn[R - 2];
-    out.q31 = qn[R - 1];
-    out.b = (w0 >> (R - 2)) & 3u;
-    out.o30 = on[R - 2];
-    out.o31 = on[R - 1];
-    h2 = h1;
-    h1 = h0;
-    w2 = w1;
-    w1 = w0;
-    return out;
-  }
-};
-
-// bnd: ceil(L / (64 R)) * ld TraceRec per pair (bnd_stride records between pairs); only read and
-// written by CRPs of more than one band. qmax_out may be NULL; seg_out: int32[4] (i0, j0, i1, j1) per pair.
-template <bool EQG, int R>
-__global__ __launch_bounds__(64) void k_crp_dp_trace(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
-                                                     const int2* __restrict__ dims, int row_lo, int row_hi, float go,
-                                                     float ge, TraceRec* __restrict__ bnd, int64_t bnd_stride,
-                                                     float* __restrict__ qmax_out, int32_t* __restrict__ seg_out) {
-  const int p = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int2 dm = dims[p];
-  const int Mp = dm.x, Np = dm.y;
-  if (!(Mp > row_lo && Mp <= row_hi)) return;  // the other R's launch takes this pair (wave-uniform)
-  constexpr int kBand = 64 * R;
-  const int nbands = (Mp + kBand - 1) / kBand;
-  DpLaneT<EQG, R> L;
-  L.go = go;
-  L.ge = ge;
-  L.Np = Np;
-  L.best = 0.0f;
-  L.bkey = L.borg = 0u;
-  for (int band = 0; band < nbands; ++band) {
-    const int row0 = band * kBand + lane * R;
-    const uint32_t* mrow = maskT + (size_t)p * mask_stride + (size_t)(row0 >> 5) * ld;
-    const int sh = row0 & 31;  // this lane's R rows inside its 32-row strip word
-    TraceRec* bout = bnd + (size_t)p * bnd_stride + (size_t)band * ld;
-    const TraceRec* bin = bnd + (size_t)p * bnd_stride + (size_t)(band - 1) * ld;
-    uint32_t rv = 0;
-    for (int r = 0; r < R; ++r) rv |= (uint32_t)((row0 + r >= 2) && (row0 + r < Mp)) << r;
-    L.rowvalid = rv;
-    L.key0 = (uint32_t)row0 << 16;
-    L.w1 = L.w2 = 0;
-    L.h1 = L.h2 = DpAboveT{0.0f, 0.0f, 0u, 0u, 0u};
-    float qa[R], qb[R], qc[R];
-    uint32_t oa[R], ob[R], oc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      qa[r] = qb[r] = qc[r] = 0.0f;
-      oa[r] = ob[r] = oc[r] = 0u;
-    }
-    DpAboveT pub{0.0f, 0.0f, 0u, 0u, 0u};
-    const int S_end = Np + 63;
-    const bool lane_active = row0 < Mp;
-    auto fetch = [&](int c) -> uint32_t {
-      if (!(lane_active && c >= 0 && c < Np)) return 0u;
-      return (mrow[c] >> sh) & ((1u << R) - 1u);
-    };
-    auto recv = [&](const DpAboveT& mine, int c) -> DpAboveT {
-      DpAboveT h;
-      h.q30 = __shfl_up(mine.q30, 1);
-      h.q31 = __shfl_up(mine.q31, 1);
-      h.b = (uint32_t)__shfl_up((int)mine.b, 1);
-      h.o30 = (uint32_t)__shfl_up((int)mine.o30, 1);
-      h.o31 = (uint32_t)__shfl_up((int)mine.o31, 1);
-      if (lane == 0) {
-        if (band > 0 && c >= 0 && c < Np) {
-          const float4 q = bin[c].q;
-          const uint4 o = bin[c].o;
-          h = DpAboveT{q.x, q.y, (uint32_t)q.z, o.x, o.y};
-        } else {
-          h = DpAboveT{0.0f, 0.0f, 0u, 0u, 0u};
-        }
-      }
-      return h;
-    };
-    auto publish = [&](const DpAboveT& o, int c) {
-      if (lane == 63 && band + 1 < nbands && c >= 0 && c < Np) {
-        bout[c].q = make_float4(o.q30, o.q31, (float)o.b, 0.0f);
-        bout[c].o = make_uint4(o.o30, o.o31, 0u, 0u);
-      }
-    };
-    uint32_t wnext = fetch(-lane);
-    for (int s = 0; s < S_end; s += 3) {
-      {
-        const int c = s - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAboveT h0 = recv(pub, c);
-        pub = L.step(qa, oa, qb, ob, qc, oc, w0, h0, c);
-        publish(pub, c);
-      }
-      if (s + 1 < S_end) {
-        const int c = s + 1 - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAboveT h0 = recv(pub, c);
-        pub = L.step(qc, oc, qa, oa, qb, ob, w0, h0, c);
-        publish(pub, c);
-      }
-      if (s + 2 < S_end) {
-        const int c = s + 2 - lane;
-        const uint32_t w0 = wnext;
-        wnext = fetch(c + 1);
-        const DpAboveT h0 = recv(pub, c);
-        pub = L.step(qb, ob, qc, oc, qa, oa, w0, h0, c);
-        publish(pub, c);
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  // wave reduction of (best, end key, origin) by the same rule as the per-cell update
-  float best = L.best;
-  uint32_t bkey = L.bkey, borg = L.borg;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v = __shfl_xor(best, o);
-    const uint32_t k = (uint32_t)__shfl_xor((int)bkey, o);
-    const uint32_t g = (uint32_t)__shfl_xor((int)borg, o);
-    if (v > best || (v == best && v > 0.0f && k < bkey)) {
-      best = v;
-      bkey = k;
-      borg = g;
-    }
-  }
-  if (lane == 0) {
-    if (qmax_out) qmax_out[p] = best;
-    const bool any = best > 0.0f;
-    int32_t* sg = seg_out + 4 * (size_t)p;
-    sg[0] = any ? (int)(borg >> 16) : -1;
-    sg[1] = any ? (int)(borg & 0xffffu) : -1;
-    sg[2] = any ? (int)(bkey >> 16) : -1;
-    sg[3] = any ? (int)(bkey & 0xffffu) : -1;
-  }
-}
-
 // Dense (M x N) uint8 CRP <-> strip words maskT[i/32][j] (bit i%32).
 __global__ void k_unpack_mask(const uint32_t* __restrict__ maskT, int ld, int M, int N, uint8_t* __restrict__ C) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1238,82 +508,6 @@ int set_lds(K kernel, size_t bytes) {
     ACOSS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return ACOSS_OK;
-}
-
-template <int ALIGN, int R>
-void launch_dp_r(bool eqg, int nb, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
-                 float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s, int L = 0) {
-  const float k2 = 2.0f * go;
-  static const bool no_fast = getenv("ACOSS_DP_NOFAST") != nullptr;
-  static const bool no_grp = getenv("ACOSS_DP_NOGROUP") != nullptr;
-  const int LP = (L + 31) / 32;  // lanes per pair at 32 rows per lane
-  if (ALIGN == 0 && eqg && !no_fast && !no_grp && k2 >= 0.0f && k2 <= 1024.0f && k2 == floorf(k2) && L > 0 &&
-      LP <= 21) {  // three or more pairs per wave (two per wave measured slower at L ~ 1000)
-    const int G = 64 / LP;
-    hipLaunchKernelGGL(k_crp_dp_grp, dim3((unsigned)((nb + G - 1) / G)), dim3(64), 0, s, maskT, mstride, ld, dims, nb,
-                       LP, go, out);
-  } else if (ALIGN == 0 && eqg && !no_fast && k2 >= 0.0f && k2 <= 1024.0f && k2 == floorf(k2))
-    hipLaunchKernelGGL((k_crp_dp_fast<R>), dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, go, ge,
-                       bnd, bstride, out);
-  else if (eqg)
-    hipLaunchKernelGGL((k_crp_dp<ALIGN, true, R>), dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, go, ge, bnd,
-                       bstride, out);
-  else
-    hipLaunchKernelGGL((k_crp_dp<ALIGN, false, R>), dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, go, ge, bnd,
-                       bstride, out);
-}
-
-// The packed 16-bit DP (k_crp_dp_pk) is exact when gamma_open == gamma_ext is a multiple of 1/2
-// and every doubled score fits 16 bits: scores grow by at most 2 per column (chen17), so 2Q < 4L.
-inline bool dp_packed_ok(bool eqg, int L, float go) {
-  static const bool off = getenv("ACOSS_DP_F32") != nullptr;
-  const float k2 = 2.0f * go;
-  return !off && eqg && L <= 16000 && k2 >= 0.0f && k2 <= 1024.0f && k2 == floorf(k2);
-}
-
-// Rows per lane from the batch's longest CRP (L rows): every choice below 2048 rows is one band,
-// so the band-boundary buffer (ceil(L / 2048) bands) always suffices.
-template <int ALIGN>
-void launch_dp(bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
-               float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s) {
-  if (L <= 512)
-    launch_dp_r<ALIGN, 8>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s, L);
-  else if (L <= 1024)
-    launch_dp_r<ALIGN, 16>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s, L);
-  else if (ALIGN == 1 && dp_packed_ok(eqg, L, go))
-    hipLaunchKernelGGL(k_crp_dp_pk<ALIGN>, dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, (unsigned)(2.0f * go), bnd,
-                       bstride, out);
-  else
-    launch_dp_r<ALIGN, 32>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s);
-}
-
-// The tracing DP (k_crp_dp_trace): R = 8 takes the CRPs of at most 512 rows, R = 16 the longer
-// ones; a batch whose longest CRP has more than 512 rows gets both launches and each wave keeps
-// the pairs of its own R. The exact-halves select (EQG) under the fast DP's condition only.
-constexpr int kTraceShortRows = 512;
-constexpr int kTraceMaxLen = 65535;  // 16 bits per coordinate of a packed cell
-
-inline int64_t trace_bnd_records(int L, int ld) {  // per pair: ceil(L / (64 R)) * ld
-  return L <= kTraceShortRows ? (int64_t)ld : (int64_t)((L + 64 * 16 - 1) / (64 * 16)) * ld;
-}
-
-template <int R>
-void launch_trace_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
-                    float go, float ge, TraceRec* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
-  const float k2 = 2.0f * go;
-  if (go == ge && k2 >= 0.0f && k2 <= 1024.0f && k2 == floorf(k2))
-    hipLaunchKernelGGL((k_crp_dp_trace<true, R>), dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, row_lo, row_hi, go,
-                       ge, bnd, bstride, qmax, seg);
-  else
-    hipLaunchKernelGGL((k_crp_dp_trace<false, R>), dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, row_lo, row_hi,
-                       go, ge, bnd, bstride, qmax, seg);
-}
-
-void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
-                  TraceRec* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
-  launch_trace_r<8>(nb, -1, kTraceShortRows, maskT, mstride, ld, dims, go, ge, bnd, bstride, qmax, seg, s);
-  if (L > kTraceShortRows)
-    launch_trace_r<16>(nb, kTraceShortRows, INT32_MAX, maskT, mstride, ld, dims, go, ge, bnd, bstride, qmax, seg, s);
 }
 
 // Per-track tables of one call, in workspace slot 0: prof (n_tracks x 12) | NX (n_tracks x ldn) |
@@ -1574,14 +768,14 @@ extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, con
     if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
     if (qmax_out) {
       prof_begin(PH_DP_QMAX, s);
-      launch_dp<0>(eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
+      launch_dp(0, eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
                    C.bnd_stride, qmax_out + base, s);
       ACOSS_LAUNCH_CHECK();
       prof_end(PH_DP_QMAX, s);
     }
     if (dmax_out) {
       prof_begin(PH_DP_DMAX, s);
-      launch_dp<1>(eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
+      launch_dp(1, eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
                    C.bnd_stride, dmax_out + base, s);
       ACOSS_LAUNCH_CHECK();
       prof_end(PH_DP_DMAX, s);
@@ -1674,10 +868,7 @@ extern "C" int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t
   hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, maskT, d_err);
   ACOSS_LAUNCH_CHECK();
   const bool eqg = gamma_open == gamma_ext;
-  if (align == 0)
-    launch_dp<0>(eqg, 1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, s);
-  else
-    launch_dp<1>(eqg, 1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, s);
+  launch_dp(align, eqg, 1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, s);
   ACOSS_LAUNCH_CHECK();
   int h_err = 0;
   ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));
@@ -1720,7 +911,7 @@ extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, co
   // band-boundary records of the tracing DP, in a slot of their own (crp_plan's carving is the
   // shipped DP's)
   const int64_t tstride = trace_bnd_records(C.L, C.ld);
-  TraceRec* tb = static_cast<TraceRec*>(workspace(22, sizeof(TraceRec) * (size_t)tstride * (size_t)C.nb_alloc));
+  void* tb = workspace(22, kTraceRecBytes * (size_t)tstride * (size_t)C.nb_alloc);
   if (!tb) return ACOSS_E_HIP;
 
   for (int64_t base = 0; base < n_pairs; base += C.nb_alloc) {
@@ -1760,12 +951,12 @@ extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float 
   const int nstrips = (M + 31) / 32;
   const int64_t trecs = trace_bnd_records(M, ld);
   const size_t mask_bytes = align_up(4 * (size_t)nstrips * ld, 256);
-  char* ws = static_cast<char*>(workspace(23, 256 + mask_bytes + sizeof(TraceRec) * (size_t)trecs));
+  char* ws = static_cast<char*>(workspace(23, 256 + mask_bytes + kTraceRecBytes * (size_t)trecs));
   if (!ws) return ACOSS_E_HIP;
   int* d_err = reinterpret_cast<int*>(ws);
   int2* d_dims = reinterpret_cast<int2*>(ws + 64);
   uint32_t* maskT = reinterpret_cast<uint32_t*>(ws + 256);
-  TraceRec* bnd = reinterpret_cast<TraceRec*>(ws + 256 + mask_bytes);
+  void* bnd = ws + 256 + mask_bytes;
   const int h_hdr[4] = {0, 0, M, N};  // err, pad, dims
   ACOSS_HIP_CHECK(hipMemcpy(d_err, h_hdr, 8, hipMemcpyHostToDevice));
   ACOSS_HIP_CHECK(hipMemcpy(d_dims, h_hdr + 2, 8, hipMemcpyHostToDevice));

@@ -1,0 +1,768 @@
+// crp_dp.hip — the Qmax (serra09) / dmax (chen17) alignment DP over the CRP words that crp.hip
+// and crp_split.hip produce: essentia CoverSongSimilarity('symmetric') restated, five kernels
+// around one wavefront walk.
+//
+// A chain of lanes owns consecutive rows of the CRP (R rows each) and sweeps the columns skewed
+// by one column per lane: lane l is at column c = s - l at step s, so the cells of one step lie
+// on an anti-diagonal and every lane has its three predecessors ready. The last two rows of a
+// lane pass down one lane per step with __shfl_up; where the CRP has more rows than a wave
+// covers, bands of 64 R rows chain through a small HBM buffer. dp_walk is that walk, written
+// once. What differs between the kernels is passed to it:
+//  * a lane policy: what a lane keeps per column and the recurrence on it (step).
+//      DpLane    f32 scores, any gamma and both alignments; FAST: serra09 at gamma = K/2
+//      DpLanePk  chen17 at gamma = K/2 in packed 16-bit integers, two rows per instruction
+//      DpLaneT   serra09 with the cell where each path began carried beside every score
+//  * an edge policy: what is above the chain's first lane and below its last one.
+//      Band       the band above / below, through HBM records
+//      GroupEdge  nothing above, nothing kept: several short pairs per wave, one band each
+//  * the lane's index in its chain, the number of steps (wave-uniform) and the fetch of a
+//    column's CRP word, which keeps each kernel's own bounds and masking.
+//
+//  k_crp_dp<ALIGN, EQG, R>   one wave per pair, DpLane in bands
+//  k_crp_dp_fast<R>          the same with the FAST step
+//  k_crp_dp_grp              FAST at 32 rows per lane, 64 / ceil(L / 32) pairs per wave
+//  k_crp_dp_pk<1>            DpLanePk in bands
+//  k_crp_dp_trace<EQG, R>    DpLaneT in bands, for acoss_crp_locate / acoss_locate_crp
+// launch_dp and launch_trace choose among them.
+#include <cstdlib>
+
+#include "crp_internal.hpp"
+
+namespace acoss {
+
+// --------------------------------------------------------------------------------------
+// The walk.
+//   Lane:  Above (what goes down one lane per column; Above{} = nothing above), Col (one column
+//          of the lane's rows), shfl_up(Above), step(new, col-1, col-2, w0, h0, c) -> Above, Np,
+//          and the walk's history w1, w2, h1, h2 that step rotates.
+//   Edge:  above(h, c, incol): h as shuffled, or what the edge supplies for the chain's first
+//          lane; below(o, c, incol): keeps o where the chain's last lane has rows below it. Both
+//          get the walk's one test of the column, incol = 0 <= c < Np, and hold whatever does not
+//          change from step to step (which lane they act on, whether a band is there) ready-made.
+//   fetch: CRP word of column c restricted to this lane's rows (0 outside the matrix).
+// --------------------------------------------------------------------------------------
+template <class Lane, class Edge, class Fetch>
+__device__ __forceinline__ void dp_walk(Lane& L, const Edge& E, int idx, int S_end, Fetch fetch) {
+  using Above = typename Lane::Above;
+  using Col = typename Lane::Col;
+  L.w1 = L.w2 = 0;
+  L.h1 = L.h2 = Above{};
+  // Three columns in rotation, so no column is ever copied: step s0 + k writes q[-k mod 3] from
+  // q[1 - k mod 3] (column c-1) and q[2 - k mod 3] (column c-2). Separate arrays behind constant
+  // indices: after the unroll each stays in registers of its own.
+  Col qa{}, qb{}, qc{};
+  Col* const q[3] = {&qa, &qb, &qc};
+  Above pub{};  // what this lane hands down, one step late
+  uint32_t wnext = fetch(-idx);
+  for (int s0 = 0; s0 < S_end; s0 += 3) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int s = s0 + k;
+      if (k > 0 && s >= S_end) break;
+      const int c = s - idx;
+      const uint32_t w0 = wnext;
+      wnext = fetch(c + 1);  // the next column's word: its latency hides behind this step
+      const bool incol = c >= 0 && c < L.Np;
+      const Above h0 = E.above(Lane::shfl_up(pub), c, incol);
+      pub = L.step(*q[(3 - k) % 3], *q[(4 - k) % 3], *q[(5 - k) % 3], w0, h0, c);
+      E.below(pub, c, incol);
+    }
+  }
+}
+
+// bit r: 2 <= row0 + r < Mp (rows 0 and 1 of the matrix hold 0, like columns 0 and 1)
+template <int R>
+__device__ __forceinline__ uint32_t row_valid_mask(int row0, int Mp) {
+  uint32_t rv = 0;
+  for (int r = 0; r < R; ++r) rv |= (uint32_t)((row0 + r >= 2) && (row0 + r < Mp)) << r;
+  return rv;
+}
+
+// Band `band` of pair p as lane `lane` sees it, at Lane::kRows rows per lane: where its rows and
+// its CRP words are, and, as the walk's edge policy, the boundary records (bnd: one row of ld
+// records per band and pair) that lane 0 reads from the band above and lane 63 writes for the
+// band below.
+template <class Lane>
+struct Band {
+  using Above = typename Lane::Above;
+  using Rec = typename Lane::Rec;
+  int row0, sh;          // this lane's first row, and its rows' place inside their 32-row strip word
+  const uint32_t* mrow;  // that strip's words, one per column
+  const Rec* bin;
+  Rec* bout;
+  bool first, reads, writes;  // lane 0; lane 0 with a band above; lane 63 with a band below
+
+  __device__ __forceinline__ Band(int p, int band, int nbands, int lane, const uint32_t* maskT,
+                                  int64_t mask_stride, int ld, Rec* bnd, int64_t bnd_stride)
+      : row0((band * 64 + lane) * Lane::kRows), sh(row0 & 31),
+        mrow(maskT + (size_t)p * mask_stride + (size_t)(row0 >> 5) * ld),
+        bin(bnd + (size_t)p * bnd_stride + (size_t)(band - 1) * ld),
+        bout(bnd + (size_t)p * bnd_stride + (size_t)band * ld),
+        first(lane == 0), reads(lane == 0 && band > 0), writes(lane == 63 && band + 1 < nbands) {}
+  __device__ __forceinline__ Above above(const Above& h, int c, bool incol) const {
+    if (!first) return h;
+    return (reads && incol) ? Lane::from_rec(bin[c]) : Above{};
+  }
+  __device__ __forceinline__ void below(const Above& o, int c, bool incol) const {
+    if (writes && incol) bout[c] = Lane::to_rec(o);
+  }
+};
+
+// A group of lanes that holds all rows of its pair: its first lane has nothing above.
+template <class Lane>
+struct GroupEdge {
+  using Above = typename Lane::Above;
+  bool first;  // the group's lane 0
+  __device__ __forceinline__ Above above(const Above& h, int, bool) const { return first ? Above{} : h; }
+  __device__ __forceinline__ void below(const Above&, int, bool) const {}
+};
+
+// --------------------------------------------------------------------------------------
+// DpLane<ALIGN, EQG, R, FAST>: f32 scores. ALIGN 0 = serra09 (Qmax), 1 = chen17 (dmax); EQG:
+// gamma_open == gamma_ext; R = 32, 16 or 8 rows per lane by the batch's longest CRP, so short
+// tracks keep every lane busy.
+// --------------------------------------------------------------------------------------
+struct DpAbove {  // what lane l-1 (or the band above) hands down for one column
+  float q30, q31;  // its last two rows (R-2, R-1)
+  uint32_t b;      // bit0 = C[row R-2], bit1 = C[row R-1]
+};
+
+// FAST (serra09 with gamma_open == gamma_ext = K/2 >= 0, the reference's setting): every score is
+// an exact multiple of 1/2, so "hit ? mx + 1 : max(mx - go, 0)" is max(fma(hit, 1 + go, mx - go), 0)
+// exactly, and the validity masks move out of the row loop: the kernel zeroes the CRP words of
+// columns < 2 and rows outside [2, Mp) at the fetch. Cells there then hold 0 (top-left: all their
+// predecessors are 0) or at most max(0, best - go) (bottom/right: no hit, and they never feed a
+// valid cell), so neither the valid scores nor their maximum change.
+// v_cvt_f32_ubyteB: byte B of v as a float (the compiler emits only the byte-0 form plus shifts).
+template <int B>
+__device__ __forceinline__ float cvt_f32_ubyte(uint32_t v) {
+  float f;
+  if constexpr (B == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(f) : "v"(v));
+  else if constexpr (B == 1) asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(f) : "v"(v));
+  else if constexpr (B == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(f) : "v"(v));
+  else asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(f) : "v"(v));
+  return f;
+}
+
+// b is a constant after the row loops unroll, so the switch folds away
+__device__ __forceinline__ float cvt_f32_ubyte_n(uint32_t v, int b) {
+  switch (b) {
+    case 0: return cvt_f32_ubyte<0>(v);
+    case 1: return cvt_f32_ubyte<1>(v);
+    case 2: return cvt_f32_ubyte<2>(v);
+    default: return cvt_f32_ubyte<3>(v);
+  }
+}
+
+template <int ALIGN, bool EQG, int R, bool FAST = false>
+struct DpLane {
+  static constexpr int kRows = R;
+  using Above = DpAbove;
+  using Rec = float4;  // q30, q31, bits as float, unused
+  using Col = float[R];  // one column: this lane's R scores
+  static __device__ __forceinline__ Above shfl_up(const Above& a) {
+    return Above{__shfl_up(a.q30, 1), __shfl_up(a.q31, 1), (uint32_t)__shfl_up((int)a.b, 1)};
+  }
+  static __device__ __forceinline__ Above from_rec(const Rec& v) { return Above{v.x, v.y, (uint32_t)v.z}; }
+  static __device__ __forceinline__ Rec to_rec(const Above& o) { return make_float4(o.q30, o.q31, (float)o.b, 0.0f); }
+
+  float go, ge;
+  int Np;
+  uint32_t rowvalid;  // bit r: 2 <= global row < Mp
+  uint32_t w1, w2;    // CRP words of columns c-1, c-2 (bit r = row r)
+  DpAbove h1, h2;     // from above for columns c-1, c-2
+  float best;
+
+  __device__ __forceinline__ float gam(uint32_t bit) const { return EQG ? go : (bit ? go : ge); }
+
+  // qn: new column c; q1: column c-1; q2: column c-2. w0: CRP word of column c;
+  // h0: from above for column c. Returns the values to hand to the lane below.
+  __device__ __forceinline__ DpAbove step(Col& qn, const Col& q1, const Col& q2, uint32_t w0, const DpAbove& h0,
+                                          int c) {
+    const bool colvalid = (c >= 2) && (c < Np);
+    const uint32_t vmask = colvalid ? rowvalid : 0u;
+    // extended words: bit r+2 <-> row r; bits 0,1 <-> rows -2,-1 (from above)
+    const uint64_t e0 = ((uint64_t)w0 << 2) | h0.b;
+    const uint64_t e1 = ((uint64_t)w1 << 2) | h1.b;
+    const uint64_t e2 = ((uint64_t)w2 << 2) | h2.b;
+    if constexpr (FAST) {
+      // two rows per v_pk_add_f32 / v_pk_fma_f32; the hit bits as bytes (rows k, k+8, k+16, k+24
+      // of one masked word), one v_cvt_f32_ubyteN each
+      typedef float dp_f32x2 __attribute__((ext_vector_type(2)));
+      const dp_f32x2 g1 = {1.0f + go, 1.0f + go};
+      const dp_f32x2 ngo = {-go, -go};
+      uint32_t bm[R < 8 ? R : 8];
+#pragma unroll
+      for (int k = 0; k < (R < 8 ? R : 8); ++k) bm[k] = (w0 >> k) & 0x01010101u;
+#pragma unroll
+      for (int r = 0; r < R; r += 2) {
+        float mxs[2], hb[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const int rr = r + e;
+          const float Qa = rr >= 1 ? q1[rr - 1] : h1.q31;
+          const float Qb = rr >= 2 ? q1[rr - 2] : (rr == 1 ? h1.q31 : h1.q30);
+          const float Qc = rr >= 1 ? q2[rr - 1] : h2.q31;
+          mxs[e] = fmaxf(fmaxf(Qa, Qb), Qc);
+          hb[e] = cvt_f32_ubyte_n(bm[rr & 7], rr >> 3);
+        }
+        const dp_f32x2 mx = {mxs[0], mxs[1]};
+        const dp_f32x2 hv = {hb[0], hb[1]};
+        const dp_f32x2 t = __builtin_elementwise_fma(hv, g1, mx + ngo);
+        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(best) : "v"(best), "v"(t.x), "v"(t.y));
+        qn[r] = fmaxf(t.x, 0.0f);
+        qn[r + 1] = fmaxf(t.y, 0.0f);
+      }
+    } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float Qa = r >= 1 ? q1[r - 1] : h1.q31;                            // Q[r-1][c-1]
+      float Qb = r >= 2 ? q1[r - 2] : (r == 1 ? h1.q31 : h1.q30);              // Q[r-2][c-1]
+      float Qc = r >= 1 ? q2[r - 1] : h2.q31;                                  // Q[r-1][c-2]
+      if (ALIGN == 1) {
+        Qb = Qb + (float)((e0 >> (r + 1)) & 1u);  // + C[r-1][c]
+        Qc = Qc + (float)((e1 >> (r + 2)) & 1u);  // + C[r][c-1]
+      }
+      const bool hit = (e0 >> (r + 2)) & 1u;
+      float v;
+      if (EQG) {
+        const float mx = fmaxf(fmaxf(Qa, Qb), Qc);
+        v = hit ? mx + 1.0f : fmaxf(mx - go, 0.0f);
+      } else {
+        const float x = Qa - gam((e1 >> (r + 1)) & 1u);  // gamma(C[r-1][c-1])
+        const float y = Qb - gam((e1 >> r) & 1u);        // gamma(C[r-2][c-1])
+        const float z = Qc - gam((e2 >> (r + 1)) & 1u);  // gamma(C[r-1][c-2])
+        const float miss = fmaxf(fmaxf(0.0f, x), fmaxf(y, z));
+        v = hit ? fmaxf(fmaxf(Qa, Qb), Qc) + 1.0f : miss;
+      }
+      v = ((vmask >> r) & 1u) ? v : 0.0f;
+      best = fmaxf(best, v);
+      qn[r] = v;
+    }
+    }
+    DpAbove out;
+    out.q30 = qn[R - 2];
+    out.q31 = qn[R - 1];
+    out.b = (w0 >> (R - 2)) & 3u;
+    h2 = h1;
+    h1 = h0;
+    w2 = w1;
+    w1 = w0;
+    return out;
+  }
+};
+
+template <int ALIGN, bool EQG, int R, bool FAST>
+__device__ __forceinline__ void crp_dp_body(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
+                                               const int2* __restrict__ dims, float go, float ge,
+                                               float4* __restrict__ bnd, int64_t bnd_stride,
+                                               float* __restrict__ out) {
+  using Lane = DpLane<ALIGN, EQG, R, FAST>;
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int2 dm = dims[p];
+  const int Mp = dm.x, Np = dm.y;
+  const int nbands = (Mp + 64 * R - 1) / (64 * R);
+  Lane L;
+  L.go = go;
+  L.ge = ge;
+  L.Np = Np;
+  L.best = 0.0f;
+  for (int band = 0; band < nbands; ++band) {
+    const Band<Lane> B(p, band, nbands, lane, maskT, mask_stride, ld, bnd, bnd_stride);
+    const uint32_t rv = L.rowvalid = row_valid_mask<R>(B.row0, Mp);
+    const bool lane_active = B.row0 < Mp;
+    dp_walk(L, B, lane, Np + 63, [&](int c) -> uint32_t {
+      if (!(lane_active && c >= (FAST ? 2 : 0) && c < Np)) return 0u;
+      const uint32_t w = B.mrow[c];
+      const uint32_t wr = R == 32 ? w : (w >> B.sh) & ((1u << (R & 31)) - 1u);
+      return FAST ? (wr & rv) : wr;
+    });
+    __threadfence_block();
+    __syncthreads();
+  }
+  const float best = wave_max(L.best);
+  if (lane == 0) out[p] = best;
+}
+
+template <int ALIGN, bool EQG, int R>
+__global__ __launch_bounds__(64) void k_crp_dp(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
+                                               const int2* __restrict__ dims, float go, float ge,
+                                               float4* __restrict__ bnd, int64_t bnd_stride,
+                                               float* __restrict__ out) {
+  crp_dp_body<ALIGN, EQG, R, false>(maskT, mask_stride, ld, dims, go, ge, bnd, bnd_stride, out);
+}
+
+// No occupancy hint: left alone the FAST body takes what it wants at R = 32 (160 VGPRs, 3 waves per
+// SIMD, today), which measured faster than forcing it into 128 (4 waves per SIMD): 14.2 vs 14.8 ms
+// per covers80 step.
+template <int R>
+__global__ __launch_bounds__(64) void k_crp_dp_fast(
+    const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld, const int2* __restrict__ dims, float go, float ge,
+    float4* __restrict__ bnd, int64_t bnd_stride, float* __restrict__ out) {
+  crp_dp_body<0, true, R, true>(maskT, mask_stride, ld, dims, go, ge, bnd, bnd_stride, out);
+}
+
+// --------------------------------------------------------------------------------------
+// k_crp_dp_grp: the FAST DP (serra09, gamma_open == gamma_ext = K/2) with SEVERAL pairs per
+// wave for CRPs of at most 2048 rows: a group of LP = ceil(L / 32) lanes per pair (lane ll owns
+// rows 32 ll .. 32 ll + 31, one band), G = 64 / LP groups per wave. A one-pair wave walks
+// N' + 63 steps however short the pair; a group walks N' + LP - 1, and every lane keeps 32 rows
+// per step, so short tracks (Da-TACOS lengths: L ~ 500) no longer leave most lanes idle or pay
+// the per-step shuffles for 8 rows. Same recurrence, same DpLane step: bit-identical scores.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_crp_dp_grp(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
+                                                   const int2* __restrict__ dims, int nb, int LP, float go,
+                                                   float* __restrict__ out) {
+  constexpr int R = 32;
+  using Lane = DpLane<0, true, R, true>;
+  __shared__ float s_best[64];
+  const int lane = threadIdx.x;
+  const int G = 64 / LP;
+  const int g = lane / LP, ll = lane - g * LP;
+  const int p = blockIdx.x * G + g;
+  const bool in_group = g < G && p < nb;
+  const int2 dm = in_group ? dims[p] : make_int2(0, 0);
+  const int Mp = dm.x, Np = dm.y;
+  const int row0 = ll * R;
+  const uint32_t* mrow = maskT + (size_t)(in_group ? p : 0) * mask_stride + (size_t)ll * ld;
+  Lane L;
+  L.go = go;
+  L.ge = go;
+  L.Np = Np;
+  L.best = 0.0f;
+  const uint32_t rv = L.rowvalid = row_valid_mask<R>(row0, Mp);
+  // steps until every group of the wave is done (wave-uniform bound)
+  const int S_end = (int)wave_max_u32(in_group ? (unsigned)(Np + LP - 1) : 0u);
+  const bool lane_active = in_group && row0 < Mp;
+  dp_walk(L, GroupEdge<Lane>{ll == 0}, ll, S_end, [&](int c) -> uint32_t {
+    if (!(lane_active && c >= 2 && c < Np)) return 0u;
+    return mrow[c] & rv;
+  });
+  // per-group maximum through LDS (groups need not be a power of two wide)
+  s_best[lane] = L.best;
+  __syncthreads();
+  if (in_group && ll == 0) {
+    float b = 0.0f;
+    for (int k = 0; k < LP; ++k) b = fmaxf(b, s_best[lane + k]);
+    out[p] = b;
+  }
+}
+
+// --------------------------------------------------------------------------------------
+// k_crp_dp_pk<ALIGN>: k_crp_dp<ALIGN, true, 32> in packed 16-bit integers. With
+// gamma_open == gamma_ext = K/2 (K a small integer, 1 for the reference's 0.5), every score is
+// a multiple of 1/2, so 2Q is an exact integer below 4 L: lane l keeps rows (h, h + 16) of a
+// column in one u32 (row h low, row h + 16 high) and takes two rows per v_pk_max_u16 /
+// v_pk_add_u16 / saturating v_pk_sub_u16 (max(x - K, 0) in one instruction). The predecessor
+// rows of pair h are pair h - 1 / h - 2 of the previous columns; pairs 0 and 1 splice in the
+// rows handed down by the lane above (v_perm). Bit-identical to the f32 kernel: both compute
+// the same exact multiples of 1/2 (the f32 values never round). Only ALIGN = 1 is launched:
+// serra09 at these gammas has the FAST step.
+// --------------------------------------------------------------------------------------
+typedef unsigned short dp_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pk16(dp_u16x2 v) { return __builtin_bit_cast(unsigned, v); }
+__device__ __forceinline__ dp_u16x2 up16(unsigned v) { return __builtin_bit_cast(dp_u16x2, v); }
+__device__ __forceinline__ unsigned pk_max16(unsigned a, unsigned b) { return pk16(__builtin_elementwise_max(up16(a), up16(b))); }
+__device__ __forceinline__ unsigned pk_add16(unsigned a, unsigned b) { return pk16(up16(a) + up16(b)); }
+__device__ __forceinline__ unsigned pk_sub16(unsigned a, unsigned b) { return pk16(up16(a) - up16(b)); }
+__device__ __forceinline__ unsigned pk_subsat16(unsigned a, unsigned b) {
+  return pk16(__builtin_elementwise_sub_sat(up16(a), up16(b)));
+}
+
+struct DpAbovePk {  // what lane l-1 (or the band above) hands down for one column
+  unsigned hq;      // its rows 30 (low half) and 31 (high half), x2 units
+  uint32_t b;       // bit0 = C[row 30], bit1 = C[row 31]
+};
+
+template <int ALIGN>
+struct DpLanePk {
+  static constexpr int kRows = 32;
+  using Above = DpAbovePk;
+  using Rec = float4;  // hq and b as bit patterns, two unused
+  using Col = unsigned[16];  // one column: rows (h, h + 16) in word h
+  static __device__ __forceinline__ Above shfl_up(const Above& a) {
+    return Above{(unsigned)__shfl_up((int)a.hq, 1), (uint32_t)__shfl_up((int)a.b, 1)};
+  }
+  static __device__ __forceinline__ Above from_rec(const Rec& v) {
+    return Above{__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y)};
+  }
+  static __device__ __forceinline__ Rec to_rec(const Above& o) {
+    return make_float4(__builtin_bit_cast(float, o.hq), __builtin_bit_cast(float, o.b), 0.0f, 0.0f);
+  }
+
+  unsigned K;          // gamma in x2 units, both halves
+  int Np;
+  uint32_t rz0, rz1;   // AND masks of pairs 0 / 1: rows 0 and 1 of the first band are 0
+  uint32_t w1, w2;     // CRP words of columns c-1, c-2
+  DpAbovePk h1, h2;    // from above for columns c-1, c-2
+  unsigned best;
+
+  __device__ __forceinline__ DpAbovePk step(Col& pn, const Col& p1, const Col& p2, uint32_t w0, const DpAbovePk& h0,
+                                            int c) {
+    const bool colok = (c >= 2) && (c < Np);
+    // rows (-1, 15) and (-2, 14) of column c-1, (-1, 15) of column c-2
+    const unsigned a0 = __builtin_amdgcn_perm(p1[15], h1.hq, 0x05040302u);
+    const unsigned b0 = __builtin_amdgcn_perm(p1[14], h1.hq, 0x05040100u);
+    const unsigned c0 = __builtin_amdgcn_perm(p2[15], h2.hq, 0x05040302u);
+#pragma unroll
+    for (int h = 0; h < 16; ++h) {
+      const unsigned A = h >= 1 ? p1[h - 1] : a0;                  // Q[r-1][c-1]
+      unsigned B = h >= 2 ? p1[h - 2] : (h == 1 ? a0 : b0);        // Q[r-2][c-1]
+      unsigned Cq = h >= 1 ? p2[h - 1] : c0;                       // Q[r-1][c-2]
+      if (ALIGN == 1) {
+        const unsigned cb = h >= 1 ? (w0 >> (h - 1)) & 0x10001u : ((h0.b >> 1) & 1u) | (((w0 >> 15) & 1u) << 16);
+        B = pk_add16(B, cb << 1);                                  // + C[r-1][c]
+        Cq = pk_add16(Cq, ((w1 >> h) & 0x10001u) << 1);            // + C[r][c-1]
+      }
+      const unsigned mx = pk_max16(pk_max16(A, B), Cq);
+      const unsigned m = pk_sub16(0u, (w0 >> h) & 0x10001u);      // 0xffff where C[r][c] = 1
+      unsigned v = (m & pk_add16(mx, 0x00020002u)) | (~m & pk_subsat16(mx, K));
+      if (h == 0) v &= rz0;
+      if (h == 1) v &= rz1;
+      v = colok ? v : 0u;
+      best = pk_max16(best, v);
+      pn[h] = v;
+    }
+    DpAbovePk out;
+    out.hq = __builtin_amdgcn_perm(pn[15], pn[14], 0x07060302u);
+    out.b = (w0 >> 30) & 3u;
+    h2 = h1;
+    h1 = h0;
+    w2 = w1;
+    w1 = w0;
+    return out;
+  }
+};
+
+// 4 waves per SIMD, no more: the body fits 96 registers (5 waves), and a launch of 4,000 pairs then
+// measured 5.0 ms against 4.2 ms at 4 waves.
+template <int ALIGN>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_crp_dp_pk(
+    const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld, const int2* __restrict__ dims, unsigned K,
+    float4* __restrict__ bnd, int64_t bnd_stride, float* __restrict__ out) {
+  using Lane = DpLanePk<ALIGN>;
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int2 dm = dims[p];
+  const int Mp = dm.x, Np = dm.y;
+  const int nbands = (Mp + 2047) / 2048;
+  Lane L;
+  L.K = K * 0x10001u;
+  L.Np = Np;
+  L.best = 0u;
+  for (int band = 0; band < nbands; ++band) {
+    const Band<Lane> B(p, band, nbands, lane, maskT, mask_stride, ld, bnd, bnd_stride);
+    L.rz0 = L.rz1 = B.row0 == 0 ? 0xffff0000u : 0xffffffffu;
+    const bool lane_active = B.row0 < Mp;
+    dp_walk(L, B, lane, Np + 63,
+            [&](int c) -> uint32_t { return (lane_active && c >= 0 && c < Np) ? B.mrow[c] : 0u; });
+    __threadfence_block();
+    __syncthreads();
+  }
+  const unsigned b2 = max(L.best & 0xffffu, L.best >> 16);
+  const float r = wave_max(0.5f * (float)b2);
+  if (lane == 0) out[p] = r;
+}
+
+// --------------------------------------------------------------------------------------
+// k_crp_dp_trace<EQG, R>: the serra09 DP of k_crp_dp<0, ., R> with ORIGIN PROPAGATION: every
+// cell carries, beside its score, the packed cell (i0 << 16) | j0 where its path began, and the
+// wave reduces (Qmax, end cell, origin of the end cell) instead of a bare maximum. Memory per
+// pair stays O(1) beyond the DP's own: no M' x N' score matrix is written.
+//  * predecessors in the fixed order a = (i-1, j-1), b = (i-2, j-1), c = (i-1, j-2); the origin is
+//    that of the FIRST predecessor attaining the maximum (raw values on a hit, penalised values
+//    on a miss; a strictly greater value replaces, an equal one does not); a hit whose
+//    predecessors are all 0 starts a path at itself.
+//  * the end cell is the first cell in row-major order holding Qmax. The skewed walk does not
+//    visit cells in row-major order, so every update compares the packed end key (i << 16) | j:
+//    v > best || (v == best && v > 0 && key < bestkey). Inside one step a lane's cells share a
+//    column and come in ascending rows, so there "first wins" is the strict compare alone.
+//  * general arithmetic, validity per cell (any gamma). EQG = true is launched only where
+//    gamma_open == gamma_ext = K/2 (K a small non-negative integer): every score is then an exact
+//    multiple of 1/2, x - gamma never rounds, and the first maximum of the penalised values is the
+//    first maximum of the raw ones, so one select serves hit and miss. Origins are defined where
+//    a path can only begin on a hit, i.e. for gamma >= 0.
+//  * R = 8 rows per lane for CRPs of at most 512 rows, R = 16 above (bands of 64 R rows): three
+//    rotating columns of R scores and R origins are 6 R live registers. A launch takes the pairs
+//    with row_lo < M' <= row_hi and leaves the others to the launch of the other R.
+//  * the values handed to the next lane, and across a band boundary through HBM, are the last two
+//    rows' scores, CRP bits and origins (TraceRec).
+// Every lane runs every step and selects; the only branches around a shuffle are wave-uniform.
+// --------------------------------------------------------------------------------------
+struct DpAboveT {   // what lane l-1 (or the band above) hands down for one column
+  float q30, q31;   // scores of its last two rows (R-2, R-1)
+  uint32_t b;       // bit0 = C[row R-2], bit1 = C[row R-1]
+  uint32_t o30, o31;  // origins of the same two cells
+};
+
+struct TraceRec {  // one column of a band boundary, 32 B
+  float4 q;        // q30, q31, bits as float, unused
+  uint4 o;         // o30, o31, unused
+};
+static_assert(sizeof(TraceRec) == kTraceRecBytes, "callers size the boundary buffer by kTraceRecBytes");
+
+template <bool EQG, int R>
+struct DpLaneT {
+  static_assert(R <= 16, "the extended CRP words are 32-bit");
+  static constexpr int kRows = R;
+  using Above = DpAboveT;
+  using Rec = TraceRec;
+  struct Col {  // scores and origins of one column
+    float q[R];
+    uint32_t o[R];
+  };
+  static __device__ __forceinline__ Above shfl_up(const Above& a) {
+    return Above{__shfl_up(a.q30, 1), __shfl_up(a.q31, 1), (uint32_t)__shfl_up((int)a.b, 1),
+                 (uint32_t)__shfl_up((int)a.o30, 1), (uint32_t)__shfl_up((int)a.o31, 1)};
+  }
+  static __device__ __forceinline__ Above from_rec(const Rec& v) {
+    return Above{v.q.x, v.q.y, (uint32_t)v.q.z, v.o.x, v.o.y};
+  }
+  static __device__ __forceinline__ Rec to_rec(const Above& a) {
+    return Rec{make_float4(a.q30, a.q31, (float)a.b, 0.0f), make_uint4(a.o30, a.o31, 0u, 0u)};
+  }
+
+  float go, ge;
+  int Np;
+  uint32_t rowvalid;  // bit r: 2 <= global row < Mp
+  uint32_t key0;      // (global row of this lane's row 0) << 16
+  uint32_t w1, w2;    // CRP words of columns c-1, c-2 (bit r = row r)
+  DpAboveT h1, h2;    // from above for columns c-1, c-2
+  float best;         // this lane's maximum so far, its end key and the origin of that cell
+  uint32_t bkey, borg;
+
+  // cn: new column c; c1: column c-1; c2: column c-2.
+  __device__ __forceinline__ DpAboveT step(Col& cn, const Col& c1, const Col& c2, uint32_t w0, const DpAboveT& h0,
+                                           int c) {
+    const bool colvalid = (c >= 2) && (c < Np);
+    const uint32_t vmask = colvalid ? rowvalid : 0u;
+    // extended words: bit r+2 <-> row r; bits 0,1 <-> rows -2,-1 (from above)
+    const uint32_t e0 = (w0 << 2) | h0.b;
+    const uint32_t e1 = (w1 << 2) | h1.b;
+    const uint32_t e2 = (w2 << 2) | h2.b;
+    const uint32_t kc = key0 + (uint32_t)c;  // key of (row 0, c); only used where colvalid
+    const float g_open = go, g_ext = ge;     // by value: a select between members is a select of addresses
+    auto gam = [&](uint32_t bit) { return bit ? g_open : g_ext; };
+    float cb = 0.0f;                         // this column's first maximum, its key and origin
+    uint32_t ck = 0u, co = 0u;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float Qa = r >= 1 ? c1.q[r - 1] : h1.q31;                        // Q[r-1][c-1]
+      const float Qb = r >= 2 ? c1.q[r - 2] : (r == 1 ? h1.q31 : h1.q30);    // Q[r-2][c-1]
+      const float Qc = r >= 1 ? c2.q[r - 1] : h2.q31;                        // Q[r-1][c-2]
+      const uint32_t Oa = r >= 1 ? c1.o[r - 1] : h1.o31;
+      const uint32_t Ob = r >= 2 ? c1.o[r - 2] : (r == 1 ? h1.o31 : h1.o30);
+      const uint32_t Oc = r >= 1 ? c2.o[r - 1] : h2.o31;
+      const bool hit = (e0 >> (r + 2)) & 1u;
+      float pa = Qa, pb = Qb, pc = Qc;
+      if (!EQG) {
+        const float x = Qa - gam((e1 >> (r + 1)) & 1u);  // gamma(C[r-1][c-1])
+        const float y = Qb - gam((e1 >> r) & 1u);        // gamma(C[r-2][c-1])
+        const float z = Qc - gam((e2 >> (r + 1)) & 1u);  // gamma(C[r-1][c-2])
+        pa = hit ? Qa : x;
+        pb = hit ? Qb : y;
+        pc = hit ? Qc : z;
+      }
+      float mx = pa;
+      uint32_t o = Oa;
+      if (pb > mx) {
+        mx = pb;
+        o = Ob;
+      }
+      if (pc > mx) {
+        mx = pc;
+        o = Oc;
+      }
+      float v = hit ? mx + 1.0f : fmaxf(EQG ? mx - g_open : mx, 0.0f);
+      const uint32_t key = kc + ((uint32_t)r << 16);
+      o = (hit && !(mx > 0.0f)) ? key : o;  // all predecessors 0: the path starts here
+      v = ((vmask >> r) & 1u) ? v : 0.0f;
+      if (v > cb) {
+        cb = v;
+        ck = key;
+        co = o;
+      }
+      // Pin the origin next to its score: the origins are first read in a later basic block
+      // (the next step's shuffles), so the compiler sinks their selects there and carries every
+      // compare mask (4 per cell, a scalar register pair each) across: 279 scalar spills at R = 16.
+      asm volatile("" : "+v"(o));
+      cn.q[r] = v;
+      cn.o[r] = o;
+    }
+    if (cb > best || (cb == best && cb > 0.0f && ck < bkey)) {
+      best = cb;
+      bkey = ck;
+      borg = co;
+    }
+    DpAboveT out;
+    out.q30 = cn.q[R - 2];
+    out.q31 = cn.q[R - 1];
+    out.b = (w0 >> (R - 2)) & 3u;
+    out.o30 = cn.o[R - 2];
+    out.o31 = cn.o[R - 1];
+    h2 = h1;
+    h1 = h0;
+    w2 = w1;
+    w1 = w0;
+    return out;
+  }
+};
+
+// bnd: ceil(L / (64 R)) * ld TraceRec per pair (bnd_stride records between pairs); only read and
+// written by CRPs of more than one band. qmax_out may be NULL; seg_out: int32[4] (i0, j0, i1, j1) per pair.
+// Waves per SIMD: R = 8 needs 96 registers, exactly the step of 5 waves, and without the floor the
+// unequal-gamma body lands at 100 (4 waves); R = 16 runs at 2 waves or better.
+template <bool EQG, int R>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R == 8 ? 5 : 2))) void k_crp_dp_trace(
+    const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld, const int2* __restrict__ dims, int row_lo,
+    int row_hi, float go, float ge, TraceRec* __restrict__ bnd, int64_t bnd_stride, float* __restrict__ qmax_out,
+    int32_t* __restrict__ seg_out) {
+  using Lane = DpLaneT<EQG, R>;
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int2 dm = dims[p];
+  const int Mp = dm.x, Np = dm.y;
+  if (!(Mp > row_lo && Mp <= row_hi)) return;  // the other R's launch takes this pair (wave-uniform)
+  const int nbands = (Mp + 64 * R - 1) / (64 * R);
+  Lane L;
+  L.go = go;
+  L.ge = ge;
+  L.Np = Np;
+  L.best = 0.0f;
+  L.bkey = L.borg = 0u;
+  for (int band = 0; band < nbands; ++band) {
+    const Band<Lane> B(p, band, nbands, lane, maskT, mask_stride, ld, bnd, bnd_stride);
+    L.rowvalid = row_valid_mask<R>(B.row0, Mp);
+    L.key0 = (uint32_t)B.row0 << 16;
+    const bool lane_active = B.row0 < Mp;
+    dp_walk(L, B, lane, Np + 63, [&](int c) -> uint32_t {
+      if (!(lane_active && c >= 0 && c < Np)) return 0u;
+      return (B.mrow[c] >> B.sh) & ((1u << R) - 1u);
+    });
+    __threadfence_block();
+    __syncthreads();
+  }
+  // wave reduction of (best, end key, origin) by the same rule as the per-cell update
+  float best = L.best;
+  uint32_t bkey = L.bkey, borg = L.borg;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v = __shfl_xor(best, o);
+    const uint32_t k = (uint32_t)__shfl_xor((int)bkey, o);
+    const uint32_t g = (uint32_t)__shfl_xor((int)borg, o);
+    if (v > best || (v == best && v > 0.0f && k < bkey)) {
+      best = v;
+      bkey = k;
+      borg = g;
+    }
+  }
+  if (lane == 0) {
+    if (qmax_out) qmax_out[p] = best;
+    const bool any = best > 0.0f;
+    int32_t* sg = seg_out + 4 * (size_t)p;
+    sg[0] = any ? (int)(borg >> 16) : -1;
+    sg[1] = any ? (int)(borg & 0xffffu) : -1;
+    sg[2] = any ? (int)(bkey >> 16) : -1;
+    sg[3] = any ? (int)(bkey & 0xffffu) : -1;
+  }
+}
+
+// --------------------------------------------------------------------------------------
+// Which kernel runs
+// --------------------------------------------------------------------------------------
+namespace {
+
+// gamma = K/2 with 0 <= K <= 1024: with equal gammas every score is an exact multiple of 1/2, what
+// the FAST step, the grouped and the packed kernel and the tracing DP's single select rest on
+inline bool half_integer_gamma(float g) {
+  const float k2 = 2.0f * g;
+  return k2 >= 0.0f && k2 <= 1024.0f && k2 == floorf(k2);
+}
+
+template <int ALIGN, int R>
+void launch_dp_r(bool eqg, int nb, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
+                 float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s, int L = 0) {
+  static const bool no_fast = getenv("ACOSS_DP_NOFAST") != nullptr;
+  static const bool no_grp = getenv("ACOSS_DP_NOGROUP") != nullptr;
+  const bool fast = ALIGN == 0 && eqg && !no_fast && half_integer_gamma(go);
+  const int LP = (L + 31) / 32;  // lanes per pair at 32 rows per lane
+  auto wave_per_pair = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, go, ge, bnd, bstride, out);
+  };
+  if (fast && !no_grp && L > 0 && LP <= 21) {  // three or more pairs per wave (two per wave measured slower at L ~ 1000)
+    const int G = 64 / LP;
+    hipLaunchKernelGGL(k_crp_dp_grp, dim3((unsigned)((nb + G - 1) / G)), dim3(64), 0, s, maskT, mstride, ld, dims, nb,
+                       LP, go, out);
+  } else if (fast)
+    wave_per_pair(k_crp_dp_fast<R>);
+  else if (eqg)
+    wave_per_pair(k_crp_dp<ALIGN, true, R>);
+  else
+    wave_per_pair(k_crp_dp<ALIGN, false, R>);
+}
+
+// The packed 16-bit DP (k_crp_dp_pk) is exact when gamma_open == gamma_ext is a multiple of 1/2
+// and every doubled score fits 16 bits: scores grow by at most 2 per column (chen17), so 2Q < 4L.
+inline bool dp_packed_ok(bool eqg, int L, float go) {
+  static const bool off = getenv("ACOSS_DP_F32") != nullptr;
+  return !off && eqg && L <= 16000 && half_integer_gamma(go);
+}
+
+// Rows per lane from the batch's longest CRP (L rows): every choice below 2048 rows is one band,
+// so the band-boundary buffer (ceil(L / 2048) bands) always suffices.
+template <int ALIGN>
+void launch_dp_a(bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
+                 float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s) {
+  if (L <= 512)
+    launch_dp_r<ALIGN, 8>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s, L);
+  else if (L <= 1024)
+    launch_dp_r<ALIGN, 16>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s, L);
+  else {
+    if constexpr (ALIGN == 1) {  // chen17 only: k_crp_dp_pk<0> is never instantiated
+      if (dp_packed_ok(eqg, L, go)) {
+        hipLaunchKernelGGL(k_crp_dp_pk<1>, dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, (unsigned)(2.0f * go),
+                           bnd, bstride, out);
+        return;
+      }
+    }
+    launch_dp_r<ALIGN, 32>(eqg, nb, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s);
+  }
+}
+
+// The tracing DP (k_crp_dp_trace): R = 8 takes the CRPs of at most 512 rows, R = 16 the longer
+// ones; a batch whose longest CRP has more than 512 rows gets both launches and each wave keeps
+// the pairs of its own R. The exact-halves select (EQG) under the fast DP's condition only.
+constexpr int kTraceShortRows = 512;
+
+template <int R>
+void launch_trace_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
+                    float go, float ge, TraceRec* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
+  const bool halves = go == ge && half_integer_gamma(go);
+  hipLaunchKernelGGL((halves ? k_crp_dp_trace<true, R> : k_crp_dp_trace<false, R>), dim3(nb), dim3(64), 0, s, maskT,
+                     mstride, ld, dims, row_lo, row_hi, go, ge, bnd, bstride, qmax, seg);
+}
+
+}  // namespace
+
+void launch_dp(int align, bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
+               float go, float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s) {
+  if (align == 0)
+    launch_dp_a<0>(eqg, nb, L, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s);
+  else
+    launch_dp_a<1>(eqg, nb, L, maskT, mstride, ld, dims, go, ge, bnd, bstride, out, s);
+}
+
+int64_t trace_bnd_records(int L, int ld) {  // per pair: ceil(L / (64 R)) * ld
+  return L <= kTraceShortRows ? (int64_t)ld : (int64_t)((L + 64 * 16 - 1) / (64 * 16)) * ld;
+}
+
+void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
+                  void* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
+  TraceRec* tb = static_cast<TraceRec*>(bnd);
+  launch_trace_r<8>(nb, -1, kTraceShortRows, maskT, mstride, ld, dims, go, ge, tb, bstride, qmax, seg, s);
+  if (L > kTraceShortRows)
+    launch_trace_r<16>(nb, kTraceShortRows, INT32_MAX, maskT, mstride, ld, dims, go, ge, tb, bstride, qmax, seg, s);
+}
+
+}  // namespace acoss

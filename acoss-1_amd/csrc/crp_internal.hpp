@@ -1,4 +1,5 @@
-// crp_internal.hpp — types shared by the Serra09/Chen kernels (crp.hip, crp_split.hip).
+// crp_internal.hpp — what the Serra09/Chen translation units (crp.hip, crp_split.hip, crp_dp.hip)
+// share.
 #pragma once
 #include "common.hpp"
 
@@ -33,5 +34,19 @@ int launch_crp_split(const CrpBatch& B, int nb, int L, float kappa, void* kplane
                      int64_t kstride,
                      uint32_t* RT, float* thr_r, float* T_r, float* thr_c, float* T_c, int64_t thr_stride,
                      uint32_t* maskT, int64_t mask_stride, int ld, hipStream_t s);
+
+// The alignment DP (crp_dp.hip) over nb pairs' CRP words maskT (mstride words between pairs, row
+// pitch ld, dims = (M', N') per pair, L = the longest M').
+// launch_dp: align 0 = Qmax (serra09), 1 = dmax (chen17); eqg: go == ge; bnd: ceil(L / 2048) * ld
+// records per pair (bstride between pairs); out[p] = the score.
+void launch_dp(int align, bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
+               float go, float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s);
+// launch_trace: Qmax (qmax may be NULL) and seg[p] = (i0, j0, i1, j1), where its alignment starts
+// and ends, for L <= kTraceMaxLen; bnd: trace_bnd_records(L, ld) records of kTraceRecBytes per pair.
+constexpr int kTraceMaxLen = 65535;  // 16 bits per coordinate of a packed cell
+constexpr size_t kTraceRecBytes = 32;
+int64_t trace_bnd_records(int L, int ld);
+void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
+                  void* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s);
 
 }  // namespace acoss

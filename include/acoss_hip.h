@@ -91,7 +91,7 @@ int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t align, flo
 /* Where the Qmax alignment lies (no counterpart call in the reference, whose CoverSongSimilarity
  * returns the whole score matrix instead): acoss_crp_align's Qmax of every pair together with
  * the first cell, in row-major order, that holds it (i1, j1) and the cell its path began at
- * (i0, j0), by origin propagation inside the DP (crp.hip k_crp_dp_trace); no M' x N' score matrix
+ * (i0, j0), by origin propagation inside the DP (crp_dp.hip k_crp_dp_trace); no M' x N' score matrix
  * is written. A path extends through the predecessors (i-1, j-1), (i-2, j-1), (i-1, j-2) in that
  * order, the first one attaining the maximum wins; a hit whose predecessors are all 0 starts one.
  * serra09 only. seg_out: int32[4 n_pairs] = (i0, j0, i1, j1) in stacked-frame rows (query) and

@@ -1,4 +1,4 @@
-"""GPU tests of the located Qmax (acoss_locate_crp / acoss_crp_locate, crp.hip k_crp_dp_trace)
+"""GPU tests of the located Qmax (acoss_locate_crp / acoss_crp_locate, crp_dp.hip k_crp_dp_trace)
 against the numpy restatement tests/qmax_trace_np.py: segments and scores compare with `==`, and
 the score also equals the shipped DP's (acoss_align_crp / acoss_crp_align) and the CPU oracle's."""
 import numpy as np
