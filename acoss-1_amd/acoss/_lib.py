@@ -49,6 +49,9 @@ SIGNATURES = {
     "acoss_align_crp": [_vp, _i32, _i32, _i32, _f32, _f32, _vp, _vp],
     "acoss_crp_locate": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _vp],
     "acoss_locate_crp": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
+    "acoss_crp_path": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _i32, _vp, _vp,
+                       _vp],
+    "acoss_path_crp": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp, _vp, _vp],
     "acoss_sw_constrained": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "acoss_csm": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "acoss_get_oti": [_vp, _vp, _i32, _vp, _vp],
@@ -288,6 +291,73 @@ def locate_crp(C, gamma_open=0.5, gamma_ext=0.5):
                               _ptr(out), _ptr(seg), _stream())
     _check(rc, "acoss_locate_crp")
     return out, seg
+
+
+PATH_CHUNK_BYTES = 1 << 30  # padded path output of one acoss_crp_path call (crp_path chunks its pairs by it)
+
+
+def _compact_paths(lens, padded):
+    """(P,) int32 lengths and (P, cap, 2) int32 padded paths -> the ragged form on the device:
+    (path_off int64 (P + 1,), cells int32 (total, 2)); pair p owns cells[path_off[p]:path_off[p + 1]]."""
+    torch = _torch()
+    keep = torch.arange(padded.shape[1], device=padded.device, dtype=torch.int32)[None, :] < lens[:, None]
+    off = torch.zeros(lens.shape[0] + 1, dtype=torch.int64, device=padded.device)
+    off[1:] = torch.cumsum(lens.to(torch.int64), 0)
+    return off, padded[keep].reshape(-1, 2)
+
+
+def crp_path(feats, track_off, track_len, max_len, pairs, params):
+    """Batched Qmax with its whole alignment path (acoss_crp_path): inputs as crp_align. Returns device
+    tensors {"qmax" (P,) f32, "seg" (P, 4) i32 and "oti" (P,) i32 as crp_locate, "path_off" (P + 1,)
+    i64, "cells" (total, 2) i32}: the path of pair p is cells[path_off[p]:path_off[p + 1]], (i, j) in
+    stacked-frame rows / columns from (i0, j0) to (i1, j1), empty where Qmax is 0. The pairs go to the
+    library in chunks whose padded output stays near PATH_CHUNK_BYTES; each is compacted on the device."""
+    torch = _torch()
+    lib = load_library()
+    feats = _dev(feats, torch.float32)
+    track_off = _dev(track_off, torch.int64)
+    track_len = _dev(track_len, torch.int32)
+    pairs, _ = _pairs_dev(pairs, int(track_len.shape[0]))
+    P = pairs.shape[0]
+    m, tau = params.m, params.tau
+    cap = max(1, 0 if max_len <= m * tau else (int(max_len) - m * tau + tau - 1) // tau)
+    q = torch.empty(P, dtype=torch.float32, device="cuda")
+    seg = torch.empty((P, 4), dtype=torch.int32, device="cuda")
+    o = torch.empty(P, dtype=torch.int32, device="cuda")
+    lens = torch.empty(P, dtype=torch.int32, device="cuda")
+    chunk = max(1, PATH_CHUNK_BYTES // (8 * cap))
+    parts = []
+    for a in range(0, P, chunk):
+        n = min(chunk, P - a)
+        padded = torch.empty((n, cap, 2), dtype=torch.int32, device="cuda")
+        rc = lib.acoss_crp_path(_ptr(feats), _ptr(track_off), _ptr(track_len), int(track_len.shape[0]), int(max_len),
+                                _ptr(pairs[a:a + n]), int(n), ctypes.byref(params), _ptr(q[a:a + n]),
+                                _ptr(seg[a:a + n]), _ptr(o[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded),
+                                _stream())
+        _check(rc, "acoss_crp_path")
+        parts.append(_compact_paths(lens[a:a + n], padded)[1])
+    off = torch.zeros(P + 1, dtype=torch.int64, device="cuda")
+    off[1:] = torch.cumsum(lens.to(torch.int64), 0)
+    cells = torch.cat(parts) if parts else torch.empty((0, 2), dtype=torch.int32, device="cuda")
+    return {"qmax": q, "seg": seg, "oti": o, "path_off": off, "cells": cells}
+
+
+def path_crp(C, gamma_open=0.5, gamma_ext=0.5, path_cap=None):
+    """Qmax of a binary (M, N) matrix and its alignment path (acoss_path_crp): (score (1,) f32, seg (4,)
+    i32, cells (len, 2) i32) device tensors; score and seg are locate_crp's. path_cap: entries of the
+    padded buffer handed to the library, min(M, N) unless given (a smaller one is refused)."""
+    torch = _torch()
+    lib = load_library()
+    C = _dev(C, torch.uint8)
+    cap = max(1, min(int(C.shape[0]), int(C.shape[1]))) if path_cap is None else int(path_cap)
+    out = torch.empty(1, dtype=torch.float32, device="cuda")
+    seg = torch.empty(4, dtype=torch.int32, device="cuda")
+    n = torch.empty(1, dtype=torch.int32, device="cuda")
+    padded = torch.empty((max(1, cap), 2), dtype=torch.int32, device="cuda")
+    rc = lib.acoss_path_crp(_ptr(C), int(C.shape[0]), int(C.shape[1]), float(gamma_open), float(gamma_ext), _ptr(out),
+                            _ptr(seg), cap, _ptr(n), _ptr(padded), _stream())
+    _check(rc, "acoss_path_crp")
+    return out, seg, padded[:int(n.item())]
 
 
 def _pack_mats(mats, dtype):

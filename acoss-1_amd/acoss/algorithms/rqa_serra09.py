@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 from .. import _lib
-from ..engine import ChromaBank, segment_frames
+from ..engine import ChromaBank, path_frames, segment_frames
 from .algorithm_template import CoverAlgorithm
 
 __all__ = ["Serra09", "ChromaBackedAlgorithm"]
@@ -88,6 +88,22 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
                                 self._n_frames[idxs[:, 1]])
         return {"qmax": r["qmax"].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": cells,
                 "query_frames": qf, "reference_frames": rf}
+
+    def align_path(self, idxs):
+        """The Qmax alignment of every (query, reference) pair of idxs, cell by cell: a dict of host
+        arrays 'qmax' (P,), 'oti' (P,) and 'cells' (P, 4) as localize, 'path_off' (P + 1,) int64,
+        'path_cells' (total, 2) int32 and 'path_frames' (total, 2) int64. The path of pair p is
+        path_cells[path_off[p]:path_off[p + 1]]: (i, j) in stacked-frame rows and columns of the
+        pair's CRP from cells[p, :2] to cells[p, 2:], each step (1, 1), (2, 1) or (1, 2);
+        path_frames holds the first frame of `chroma_type` before downsampling of each of them
+        (engine.path_frames). A pair whose Qmax is 0 has an empty path. Not collective."""
+        self.prepare()
+        idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
+        r = self._bank.crp_path(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti)
+        pc = r["cells"].cpu().numpy()
+        return {"qmax": r["qmax"].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": r["seg"].cpu().numpy(),
+                "path_off": r["path_off"].cpu().numpy(), "path_cells": pc,
+                "path_frames": path_frames(pc, self.tau, self.downsample_fac)}
 
     def _norm_factors(self):
         """sqrt(n_j) in float64, n_j = downsampled frames of song j."""

@@ -41,6 +41,14 @@ def segment_frames(seg, m, tau, factor, n_query, n_reference):
     return out[0], out[1]
 
 
+def path_frames(cells, tau, factor):
+    """Cells of alignment paths -> original feature frames (pure numpy). cells: (n, 2) (i, j) in
+    stacked-frame rows (query) and columns (reference). Stacked row i starts at downsampled frame
+    i*tau, which starts at original frame i*tau*factor: the convention of segment_frames' lower
+    ends. Returns (n, 2) int64 (query frame, reference frame)."""
+    return np.asarray(cells, np.int64).reshape(-1, 2) * (int(tau) * int(factor))
+
+
 class ChromaBank:
     """12-bin chroma of a whole corpus resident on the current GPU."""
 
@@ -103,3 +111,18 @@ class ChromaBank:
                     "oti": torch.zeros(0, dtype=torch.int32, device="cuda")}
         params = _lib.crp_params(m, tau, kappa, oti, gamma_open, gamma_ext)
         return _lib.crp_locate(self.feats, self.off, self.len, self.max_len, pairs, params)
+
+    def crp_path(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5):
+        """Qmax of (query, reference) pairs with the whole alignment path of each: {"qmax", "seg"
+        (P, 4), "oti", "path_off" (P + 1,), "cells" (total, 2)} device tensors (see _lib.crp_path);
+        scores and segments are crp_locate's."""
+        torch = _lib._torch()
+        pairs = self._pairs(pairs, m, tau)
+        if pairs is None:
+            return {"qmax": torch.zeros(0, dtype=torch.float32, device="cuda"),
+                    "seg": torch.zeros((0, 4), dtype=torch.int32, device="cuda"),
+                    "oti": torch.zeros(0, dtype=torch.int32, device="cuda"),
+                    "path_off": torch.zeros(1, dtype=torch.int64, device="cuda"),
+                    "cells": torch.zeros((0, 2), dtype=torch.int32, device="cuda")}
+        params = _lib.crp_params(m, tau, kappa, oti, gamma_open, gamma_ext)
+        return _lib.crp_path(self.feats, self.off, self.len, self.max_len, pairs, params)

@@ -22,8 +22,9 @@
 //    later evaluated in the squared domain (sq_threshold), so no per-cell sqrt is needed.
 //  * k_crp_panel: recomputes the distances of a 32-row x 256-column panel and writes the
 //    CRP as one 32-bit word per (32-row strip, column): the layout the DP consumes.
-// The wavefront DP over those words (k_crp_dp*, and k_crp_dp_trace for acoss_crp_locate /
-// acoss_locate_crp) is crp_dp.hip; this file reaches it through launch_dp and launch_trace.
+// The wavefront DP over those words (k_crp_dp*, k_crp_dp_trace for acoss_crp_locate /
+// acoss_locate_crp, k_crp_dp_dir and k_crp_backtrack for acoss_crp_path / acoss_path_crp) is
+// crp_dp.hip; this file reaches it through launch_dp, launch_trace, launch_dir and launch_backtrack.
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -963,6 +964,143 @@ extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float 
   hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, maskT, d_err);
   ACOSS_LAUNCH_CHECK();
   launch_trace(1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, seg_out, s);
+  ACOSS_LAUNCH_CHECK();
+  int h_err = 0;
+  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  if (h_err) {
+    set_error("CoverSongSimilarity: non-binary elements found in the input similarity matrix");
+    return ACOSS_E_NONBINARY;
+  }
+  return ACOSS_OK;
+}
+
+// The direction plane of one DP batch stays under this many bytes (acoss_crp_path shrinks its DP
+// batch below crp_plan's where needed): 1 MB per pair at 2,000 frames still gives a launch of
+// about 4,000 waves.
+static size_t path_plane_budget() {
+  size_t budget = (size_t)4 << 30;
+  if (const char* e = getenv("ACOSS_PATH_BYTES")) budget = strtoull(e, nullptr, 10);
+  return budget;
+}
+
+extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                              int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                              const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                              int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  clear_error();
+  int rc = check_params(params);
+  if (rc) return rc;
+  if (n_pairs < 0 || n_tracks < 0 || max_len < 0 || path_cap < 0) {
+    set_error("negative size");
+    return ACOSS_E_ARG;
+  }
+  if (n_pairs == 0) return ACOSS_OK;
+  if (!feats || !track_off || !track_len || !pairs || !len_out || !path_out) {
+    set_error("NULL input pointer, len_out or path_out");
+    return ACOSS_E_ARG;
+  }
+  const int Lmax = stacked_len(max_len, params->m, params->tau);
+  if (Lmax > kTraceMaxLen) {
+    set_error("stacked length %d above %d: a packed cell has 16 bits per coordinate", Lmax, kTraceMaxLen);
+    return ACOSS_E_SHAPE;
+  }
+  if (path_cap < Lmax) {
+    set_error("path_cap %d below the longest stacked length %d: a path may have that many cells", path_cap, Lmax);
+    return ACOSS_E_ARG;
+  }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  CrpPlan C;
+  if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, s, C))) return rc;
+  TrackPrep T;
+  prof_begin(PH_PREP, s);
+  if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, C.m, C.tau, s, &T))) return rc;
+  prof_end(PH_PREP, s);
+  // the direction DP's plane, band-boundary records and end keys in a slot of their own; the DP
+  // batch is crp_plan's unless its planes would pass the budget
+  const int64_t pstride = (int64_t)align_up((size_t)dir_plane_bytes(C.L, C.ld), 256);
+  const int64_t bstride = trace_bnd_records(C.L, C.ld);
+  int64_t nbp = (int64_t)(path_plane_budget() / (size_t)pstride);
+  if (nbp < 1) nbp = 1;
+  if (nbp > C.nb_alloc) nbp = C.nb_alloc;
+  // batches of equal size: a last batch of a few pairs would be a launch that fills no GPU
+  const int64_t nbatches = (n_pairs + nbp - 1) / nbp;
+  nbp = (n_pairs + nbatches - 1) / nbatches;
+  const size_t plane_bytes = (size_t)pstride * (size_t)nbp;
+  const size_t bnd_bytes = align_up(sizeof(float4) * (size_t)bstride * (size_t)nbp, 256);
+  char* ws = static_cast<char*>(workspace(24, plane_bytes + bnd_bytes + 4 * (size_t)nbp));
+  if (!ws) return ACOSS_E_HIP;
+  uint8_t* plane = reinterpret_cast<uint8_t*>(ws);
+  float4* bnd = reinterpret_cast<float4*>(ws + plane_bytes);
+  uint32_t* endkey = reinterpret_cast<uint32_t*>(ws + plane_bytes + bnd_bytes);
+
+  for (int64_t base = 0; base < n_pairs; base += nbp) {
+    const int nb = (int)((n_pairs - base) < nbp ? (n_pairs - base) : nbp);
+    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
+    prof_begin(PH_DP_DIR, s);
+    launch_dir(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, bnd, bstride,
+               plane, pstride, endkey, qmax_out ? qmax_out + base : nullptr, s);
+    ACOSS_LAUNCH_CHECK();
+    prof_end(PH_DP_DIR, s);
+    prof_begin(PH_BACKTRACK, s);
+    launch_backtrack(nb, plane, pstride, C.ld, C.dims, endkey, path_cap, seg_out ? seg_out + 4 * base : nullptr,
+                     len_out + base, path_out + 2 * (size_t)path_cap * (size_t)base, s);
+    ACOSS_LAUNCH_CHECK();
+    prof_end(PH_BACKTRACK, s);
+    if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
+  }
+  return ACOSS_OK;
+}
+
+extern "C" int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                              float* score_out, int32_t* seg_out, int32_t path_cap, int32_t* len_out,
+                              int32_t* path_out, void* hip_stream) {
+  clear_error();
+  if (M < 0 || N < 0 || path_cap < 0 || !score_out || !len_out || !path_out) {
+    set_error("bad arguments to acoss_path_crp");
+    return ACOSS_E_ARG;
+  }
+  if (M > kTraceMaxLen || N > kTraceMaxLen) {
+    set_error("matrix %d x %d above %d rows or columns: a packed cell has 16 bits per coordinate", M, N, kTraceMaxLen);
+    return ACOSS_E_SHAPE;
+  }
+  if (path_cap < (M < N ? M : N)) {
+    set_error("path_cap %d below min(M, N) = %d: a path may have that many cells", path_cap, M < N ? M : N);
+    return ACOSS_E_ARG;
+  }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if (M == 0 || N == 0) {
+    if (path_cap > 0) ACOSS_HIP_CHECK(hipMemsetAsync(path_out, 0xff, 8 * (size_t)path_cap, s));
+    const float z = 0.0f;
+    const int32_t none[4] = {-1, -1, -1, -1};
+    const int32_t zero = 0;
+    ACOSS_HIP_CHECK(hipMemcpyAsync(score_out, &z, 4, hipMemcpyHostToDevice, s));
+    if (seg_out) ACOSS_HIP_CHECK(hipMemcpyAsync(seg_out, none, sizeof(none), hipMemcpyHostToDevice, s));
+    ACOSS_HIP_CHECK(hipMemcpyAsync(len_out, &zero, 4, hipMemcpyHostToDevice, s));
+    ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+    return ACOSS_OK;
+  }
+  const int ld = (int)align_up((size_t)N, 8);
+  const int nstrips = (M + 31) / 32;
+  const size_t mask_bytes = align_up(4 * (size_t)nstrips * ld, 256);
+  const size_t bnd_bytes = align_up(sizeof(float4) * (size_t)trace_bnd_records(M, ld), 256);
+  const size_t plane_bytes = (size_t)dir_plane_bytes(M, ld);
+  char* ws = static_cast<char*>(workspace(25, 256 + mask_bytes + bnd_bytes + plane_bytes));
+  if (!ws) return ACOSS_E_HIP;
+  int* d_err = reinterpret_cast<int*>(ws);
+  int2* d_dims = reinterpret_cast<int2*>(ws + 64);
+  uint32_t* d_end = reinterpret_cast<uint32_t*>(ws + 128);
+  uint32_t* maskT = reinterpret_cast<uint32_t*>(ws + 256);
+  float4* bnd = reinterpret_cast<float4*>(ws + 256 + mask_bytes);
+  uint8_t* plane = reinterpret_cast<uint8_t*>(ws + 256 + mask_bytes + bnd_bytes);
+  const int h_hdr[4] = {0, 0, M, N};  // err, pad, dims
+  ACOSS_HIP_CHECK(hipMemcpy(d_err, h_hdr, 8, hipMemcpyHostToDevice));
+  ACOSS_HIP_CHECK(hipMemcpy(d_dims, h_hdr + 2, 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, maskT, d_err);
+  ACOSS_LAUNCH_CHECK();
+  launch_dir(1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, plane, 0, d_end, score_out, s);
+  ACOSS_LAUNCH_CHECK();
+  launch_backtrack(1, plane, 0, ld, d_dims, d_end, path_cap, seg_out, len_out, path_out, s);
   ACOSS_LAUNCH_CHECK();
   int h_err = 0;
   ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));

@@ -1,5 +1,5 @@
 // crp_dp.hip — the Qmax (serra09) / dmax (chen17) alignment DP over the CRP words that crp.hip
-// and crp_split.hip produce: essentia CoverSongSimilarity('symmetric') restated, five kernels
+// and crp_split.hip produce: essentia CoverSongSimilarity('symmetric') restated, six kernels
 // around one wavefront walk.
 //
 // A chain of lanes owns consecutive rows of the CRP (R rows each) and sweeps the columns skewed
@@ -12,6 +12,7 @@
 //      DpLane    f32 scores, any gamma and both alignments; FAST: serra09 at gamma = K/2
 //      DpLanePk  chen17 at gamma = K/2 in packed 16-bit integers, two rows per instruction
 //      DpLaneT   serra09 with the cell where each path began carried beside every score
+//      DpLaneD   serra09 scores that leave a 2-bit predecessor code per cell in a plane
 //  * an edge policy: what is above the chain's first lane and below its last one.
 //      Band       the band above / below, through HBM records
 //      GroupEdge  nothing above, nothing kept: several short pairs per wave, one band each
@@ -23,7 +24,9 @@
 //  k_crp_dp_grp              FAST at 32 rows per lane, 64 / ceil(L / 32) pairs per wave
 //  k_crp_dp_pk<1>            DpLanePk in bands
 //  k_crp_dp_trace<EQG, R>    DpLaneT in bands, for acoss_crp_locate / acoss_locate_crp
-// launch_dp and launch_trace choose among them.
+//  k_crp_dp_dir<EQG, R>      DpLaneD in bands, and k_crp_backtrack, the walk back over its plane,
+//                            for acoss_crp_path / acoss_path_crp
+// launch_dp, launch_trace and launch_dir choose among them.
 #include <cstdlib>
 
 #include "crp_internal.hpp"
@@ -669,6 +672,252 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R == 8 ? 5 :
 }
 
 // --------------------------------------------------------------------------------------
+// k_crp_dp_dir<EQG, R>: the serra09 DP of k_crp_dp_trace with, instead of an origin beside every
+// score, a 2-BIT DIRECTION per cell written to a per-pair plane, so that k_crp_backtrack can
+// follow the Qmax alignment cell by cell (acoss_crp_path / acoss_path_crp).
+//  * scores only: the lane, its columns and what it hands down are DpLane's (DpAbove, float4
+//    band records); same arithmetic and same choice of predecessor as DpLaneT, EQG included.
+//  * code of a cell: 0 = no predecessor (its score is 0, or it is a hit whose predecessors are
+//    all 0: a path starts there), 1 / 2 / 3 = a / b / c, the first one attaining the maximum.
+//    Cells outside validity have score 0 and so code 0.
+//  * the codes of a lane's R rows in one column are one word of 2 R bits (row r in bits 2r,
+//    2r + 1), stored once per step with a plain vector store. Plane of a pair: row groups of R
+//    rows, ld words each: word (i / R) * ld + j holds cell (i, j); 16-bit words at R = 8, 32-bit
+//    at R = 16, both M' N' / 4 bytes. A lane that owns rows of the matrix stores every column, so
+//    every word a walk can reach is written and the plane is never zeroed.
+//  * R and the bands are the tracing DP's: R = 8 up to 512 rows, 16 above, by the same two
+//    launches; the wave reduces (Qmax, end key) by its rule and leaves the key in endkey[p].
+// The store sits after the step's shuffles, under the lane's own predicate; every lane runs every
+// step.
+// --------------------------------------------------------------------------------------
+constexpr int kTraceShortRows = 512;  // R = 8 up to here, R = 16 above (tracing and direction DP)
+
+template <int R>
+struct DirWord {
+  using type = uint32_t;
+};
+template <>
+struct DirWord<8> {
+  using type = uint16_t;
+};
+
+template <bool EQG, int R>
+struct DpLaneD {
+  static_assert(R == 8 || R == 16, "2 R code bits are one 16- or 32-bit word");
+  static constexpr int kRows = R;
+  using Above = DpAbove;
+  using Rec = float4;  // q30, q31, bits as float, unused
+  using Col = float[R];
+  using Word = typename DirWord<R>::type;
+  static __device__ __forceinline__ Above shfl_up(const Above& a) {
+    return Above{__shfl_up(a.q30, 1), __shfl_up(a.q31, 1), (uint32_t)__shfl_up((int)a.b, 1)};
+  }
+  static __device__ __forceinline__ Above from_rec(const Rec& v) { return Above{v.x, v.y, (uint32_t)v.z}; }
+  static __device__ __forceinline__ Rec to_rec(const Above& o) { return make_float4(o.q30, o.q31, (float)o.b, 0.0f); }
+
+  float go, ge;
+  int Np;
+  uint32_t rowvalid;  // bit r: 2 <= global row < Mp
+  uint32_t key0;      // (global row of this lane's row 0) << 16
+  uint32_t w1, w2;    // CRP words of columns c-1, c-2 (bit r = row r)
+  DpAbove h1, h2;     // from above for columns c-1, c-2
+  float best;         // this lane's maximum so far and its end key
+  uint32_t bkey;
+  Word* drow;         // this lane's row group of the direction plane, one word per column
+  bool stores;        // the lane owns rows of the matrix
+
+  __device__ __forceinline__ DpAbove step(Col& qn, const Col& q1, const Col& q2, uint32_t w0, const DpAbove& h0,
+                                          int c) {
+    const bool colvalid = (c >= 2) && (c < Np);
+    const uint32_t vmask = colvalid ? rowvalid : 0u;
+    // extended words: bit r+2 <-> row r; bits 0,1 <-> rows -2,-1 (from above)
+    const uint32_t e0 = (w0 << 2) | h0.b;
+    const uint32_t e1 = (w1 << 2) | h1.b;
+    const uint32_t e2 = (w2 << 2) | h2.b;
+    const uint32_t kc = key0 + (uint32_t)c;  // key of (row 0, c); only used where colvalid
+    const float g_open = go, g_ext = ge;
+    auto gam = [&](uint32_t bit) { return bit ? g_open : g_ext; };
+    float cb = 0.0f;  // this column's first maximum and its key
+    uint32_t ck = 0u;
+    uint32_t word = 0u;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float Qa = r >= 1 ? q1[r - 1] : h1.q31;                        // Q[r-1][c-1]
+      const float Qb = r >= 2 ? q1[r - 2] : (r == 1 ? h1.q31 : h1.q30);    // Q[r-2][c-1]
+      const float Qc = r >= 1 ? q2[r - 1] : h2.q31;                        // Q[r-1][c-2]
+      const bool hit = (e0 >> (r + 2)) & 1u;
+      float pa = Qa, pb = Qb, pc = Qc;
+      if (!EQG) {
+        const float x = Qa - gam((e1 >> (r + 1)) & 1u);  // gamma(C[r-1][c-1])
+        const float y = Qb - gam((e1 >> r) & 1u);        // gamma(C[r-2][c-1])
+        const float z = Qc - gam((e2 >> (r + 1)) & 1u);  // gamma(C[r-1][c-2])
+        pa = hit ? Qa : x;
+        pb = hit ? Qb : y;
+        pc = hit ? Qc : z;
+      }
+      float mx = pa;
+      uint32_t k = 1u;
+      if (pb > mx) {
+        mx = pb;
+        k = 2u;
+      }
+      if (pc > mx) {
+        mx = pc;
+        k = 3u;
+      }
+      float v = hit ? mx + 1.0f : fmaxf(EQG ? mx - g_open : mx, 0.0f);
+      k = (hit && !(mx > 0.0f)) ? 0u : k;  // all predecessors 0: the path starts here
+      v = ((vmask >> r) & 1u) ? v : 0.0f;
+      k = v > 0.0f ? k : 0u;
+      word |= k << (2 * r);
+      // Pin the word row by row: it is first read at the store below, and left alone the compiler
+      // sinks every code's selects there and carries their compare masks (a scalar register pair
+      // each) across the row loop: 79 scalar spills at R = 16.
+      asm volatile("" : "+v"(word));
+      if (v > cb) {
+        cb = v;
+        ck = kc + ((uint32_t)r << 16);
+      }
+      qn[r] = v;
+    }
+    if (cb > best || (cb == best && cb > 0.0f && ck < bkey)) {
+      best = cb;
+      bkey = ck;
+    }
+    if (stores && c >= 0 && c < Np) drow[c] = (Word)word;
+    DpAbove out;
+    out.q30 = qn[R - 2];
+    out.q31 = qn[R - 1];
+    out.b = (w0 >> (R - 2)) & 3u;
+    h2 = h1;
+    h1 = h0;
+    w2 = w1;
+    w1 = w0;
+    return out;
+  }
+};
+
+// bnd: ceil(L / (64 R)) * ld float4 per pair, as the tracing DP's records are counted; plane:
+// pstride bytes between pairs. qmax_out may be NULL.
+template <bool EQG, int R>
+__global__ __launch_bounds__(64) void k_crp_dp_dir(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
+                                                   const int2* __restrict__ dims, int row_lo, int row_hi, float go,
+                                                   float ge, float4* __restrict__ bnd, int64_t bnd_stride,
+                                                   uint8_t* __restrict__ plane, int64_t plane_stride,
+                                                   uint32_t* __restrict__ endkey, float* __restrict__ qmax_out) {
+  using Lane = DpLaneD<EQG, R>;
+  using Word = typename Lane::Word;
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int2 dm = dims[p];
+  const int Mp = dm.x, Np = dm.y;
+  if (!(Mp > row_lo && Mp <= row_hi)) return;  // the other R's launch takes this pair (wave-uniform)
+  const int nbands = (Mp + 64 * R - 1) / (64 * R);
+  Word* const pl = reinterpret_cast<Word*>(plane + (size_t)p * plane_stride);
+  Lane L;
+  L.go = go;
+  L.ge = ge;
+  L.Np = Np;
+  L.best = 0.0f;
+  L.bkey = 0u;
+  for (int band = 0; band < nbands; ++band) {
+    const Band<Lane> B(p, band, nbands, lane, maskT, mask_stride, ld, bnd, bnd_stride);
+    L.rowvalid = row_valid_mask<R>(B.row0, Mp);
+    L.key0 = (uint32_t)B.row0 << 16;
+    const bool lane_active = B.row0 < Mp;
+    L.drow = pl + (size_t)(band * 64 + lane) * ld;
+    L.stores = lane_active;
+    dp_walk(L, B, lane, Np + 63, [&](int c) -> uint32_t {
+      if (!(lane_active && c >= 0 && c < Np)) return 0u;
+      return (B.mrow[c] >> B.sh) & ((1u << R) - 1u);
+    });
+    __threadfence_block();
+    __syncthreads();
+  }
+  float best = L.best;
+  uint32_t bkey = L.bkey;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v = __shfl_xor(best, o);
+    const uint32_t k = (uint32_t)__shfl_xor((int)bkey, o);
+    if (v > best || (v == best && v > 0.0f && k < bkey)) {
+      best = v;
+      bkey = k;
+    }
+  }
+  if (lane == 0) {
+    if (qmax_out) qmax_out[p] = best;
+    endkey[p] = best > 0.0f ? bkey : kNoEnd;
+  }
+}
+
+// --------------------------------------------------------------------------------------
+// k_crp_backtrack: one wave per pair. Lane 0 walks the direction plane from the end cell: note the
+// cell, read its code, step to the predecessor, stop at code 0. The walk is a counted loop of at
+// most min(M', N', path_cap) cells that also ends when a step would leave the matrix, so whatever
+// the plane holds it ends and reads inside the pair's plane. The cells land in path[] last to
+// first; then the whole wave turns them round in place and fills the rest of the pair's path_cap
+// entries with -1. seg (unless NULL): the first and last cell, (-1, -1, -1, -1) for no path.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_crp_backtrack(const uint8_t* __restrict__ plane, int64_t plane_stride, int ld,
+                                                      const int2* __restrict__ dims,
+                                                      const uint32_t* __restrict__ endkey, int path_cap,
+                                                      int32_t* __restrict__ seg_out, int32_t* __restrict__ len_out,
+                                                      int32_t* path_out) {
+  __shared__ int s_n;
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  int2* const out = reinterpret_cast<int2*>(path_out) + (size_t)p * path_cap;
+  if (lane == 0) {
+    const int2 dm = dims[p];
+    const int Mp = dm.x, Np = dm.y;
+    const uint32_t key = endkey[p];
+    int i = (int)(key >> 16), j = (int)(key & 0xffffu);
+    int n = 0, i0 = -1, j0 = -1, i1 = -1, j1 = -1;
+    if (key != kNoEnd && i >= 2 && i < Mp && j >= 2 && j < Np) {
+      const uint8_t* const pl = plane + (size_t)p * plane_stride;
+      const bool r8 = Mp <= kTraceShortRows;
+      const int lim = min(min(Mp, Np), path_cap);
+      i1 = i;
+      j1 = j;
+      while (n < lim) {
+        out[n++] = make_int2(i, j);
+        i0 = i;
+        j0 = j;
+        uint32_t code;
+        if (r8)
+          code = reinterpret_cast<const uint16_t*>(pl)[(size_t)(i >> 3) * ld + j] >> (2 * (i & 7));
+        else
+          code = reinterpret_cast<const uint32_t*>(pl)[(size_t)(i >> 4) * ld + j] >> (2 * (i & 15));
+        code &= 3u;
+        if (code == 0u) break;
+        i -= code == 2u ? 2 : 1;
+        j -= code == 3u ? 2 : 1;
+        if (i < 2 || j < 2) break;
+      }
+    }
+    if (seg_out) {
+      int32_t* sg = seg_out + 4 * (size_t)p;
+      sg[0] = i0;
+      sg[1] = j0;
+      sg[2] = i1;
+      sg[3] = j1;
+    }
+    len_out[p] = n;
+    s_n = n;
+  }
+  __threadfence_block();
+  __syncthreads();
+  const int n = s_n;
+  for (int t = lane; t < n / 2; t += 64) {
+    const int2 a = out[t], b = out[n - 1 - t];
+    out[t] = b;
+    out[n - 1 - t] = a;
+  }
+  for (int t = n + lane; t < path_cap; t += 64) out[t] = make_int2(-1, -1);
+}
+
+// --------------------------------------------------------------------------------------
 // Which kernel runs
 // --------------------------------------------------------------------------------------
 namespace {
@@ -732,8 +981,8 @@ void launch_dp_a(bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride
 
 // The tracing DP (k_crp_dp_trace): R = 8 takes the CRPs of at most 512 rows, R = 16 the longer
 // ones; a batch whose longest CRP has more than 512 rows gets both launches and each wave keeps
-// the pairs of its own R. The exact-halves select (EQG) under the fast DP's condition only.
-constexpr int kTraceShortRows = 512;
+// the pairs of its own R. The exact-halves select (EQG) under the fast DP's condition only. The
+// direction DP (k_crp_dp_dir) is launched the same way.
 
 template <int R>
 void launch_trace_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
@@ -741,6 +990,15 @@ void launch_trace_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64
   const bool halves = go == ge && half_integer_gamma(go);
   hipLaunchKernelGGL((halves ? k_crp_dp_trace<true, R> : k_crp_dp_trace<false, R>), dim3(nb), dim3(64), 0, s, maskT,
                      mstride, ld, dims, row_lo, row_hi, go, ge, bnd, bstride, qmax, seg);
+}
+
+template <int R>
+void launch_dir_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
+                  float go, float ge, float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey,
+                  float* qmax, hipStream_t s) {
+  const bool halves = go == ge && half_integer_gamma(go);
+  hipLaunchKernelGGL((halves ? k_crp_dp_dir<true, R> : k_crp_dp_dir<false, R>), dim3(nb), dim3(64), 0, s, maskT,
+                     mstride, ld, dims, row_lo, row_hi, go, ge, bnd, bstride, plane, pstride, endkey, qmax);
 }
 
 }  // namespace
@@ -763,6 +1021,26 @@ void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld,
   launch_trace_r<8>(nb, -1, kTraceShortRows, maskT, mstride, ld, dims, go, ge, tb, bstride, qmax, seg, s);
   if (L > kTraceShortRows)
     launch_trace_r<16>(nb, kTraceShortRows, INT32_MAX, maskT, mstride, ld, dims, go, ge, tb, bstride, qmax, seg, s);
+}
+
+// per pair: ceil(L / 16) row groups of ld 32-bit words; the 16-bit words of the 8-row groups of a
+// CRP of at most 512 rows never take more
+int64_t dir_plane_bytes(int L, int ld) { return (int64_t)((L + 15) / 16) * ld * 4; }
+
+void launch_dir(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
+                float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey, float* qmax,
+                hipStream_t s) {
+  launch_dir_r<8>(nb, -1, kTraceShortRows, maskT, mstride, ld, dims, go, ge, bnd, bstride, plane, pstride, endkey,
+                  qmax, s);
+  if (L > kTraceShortRows)
+    launch_dir_r<16>(nb, kTraceShortRows, INT32_MAX, maskT, mstride, ld, dims, go, ge, bnd, bstride, plane, pstride,
+                     endkey, qmax, s);
+}
+
+void launch_backtrack(int nb, const uint8_t* plane, int64_t pstride, int ld, const int2* dims, const uint32_t* endkey,
+                      int path_cap, int32_t* seg, int32_t* len, int32_t* path, hipStream_t s) {
+  hipLaunchKernelGGL(k_crp_backtrack, dim3(nb), dim3(64), 0, s, plane, pstride, ld, dims, endkey, path_cap, seg, len,
+                     path);
 }
 
 }  // namespace acoss

@@ -48,5 +48,18 @@ constexpr size_t kTraceRecBytes = 32;
 int64_t trace_bnd_records(int L, int ld);
 void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
                   void* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s);
+// The Qmax alignment path, cell by cell, for L <= kTraceMaxLen. launch_dir: the direction DP; per
+// pair it fills a plane of 2-bit predecessor codes (dir_plane_bytes(L, ld) bytes, pstride bytes
+// between pairs) and endkey[p] = (i1 << 16) | j1 (kNoEnd where Qmax is 0); qmax may be NULL; bnd:
+// trace_bnd_records(L, ld) float4 records per pair. launch_backtrack: walks each pair's plane from
+// its end cell and writes len[p] cells (i, j), first to last, to path + 2 path_cap p (the rest -1)
+// and, unless seg is NULL, launch_trace's seg[p].
+constexpr uint32_t kNoEnd = 0xffffffffu;
+int64_t dir_plane_bytes(int L, int ld);
+void launch_dir(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
+                float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey, float* qmax,
+                hipStream_t s);
+void launch_backtrack(int nb, const uint8_t* plane, int64_t pstride, int ld, const int2* dims, const uint32_t* endkey,
+                      int path_cap, int32_t* seg, int32_t* len, int32_t* path, hipStream_t s);
 
 }  // namespace acoss

@@ -107,6 +107,32 @@ int acoss_crp_locate(const float* feats, const int64_t* track_off, const int32_t
 int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
                      float* score_out, int32_t* seg_out, void* hip_stream);
 
+/* The Qmax alignment itself: every cell of the path acoss_crp_locate gives the two ends of, i.e.
+ * which query frame goes with which reference frame (the reference leaves this backtrack over
+ * CoverSongSimilarity's score matrix to its caller). A direction DP (crp_dp.hip k_crp_dp_dir)
+ * writes a 2-bit predecessor code per cell to a per-pair plane in the workspace (about M' N' / 4
+ * bytes; the plane of one DP batch stays under 4 GiB or ACOSS_PATH_BYTES, by a smaller DP batch
+ * where needed), and k_crp_backtrack walks it from the end cell. The path of a pair is the chain
+ * of chosen predecessors (same order and tie rule as acoss_crp_locate) from (i1, j1) back to a
+ * cell without one, reported from (i0, j0) to (i1, j1): strictly increasing in i and j, steps
+ * (1, 1), (2, 1), (1, 2), at most min(M', N') cells, empty where Qmax is 0. serra09 only.
+ * path_out: int32[n_pairs][path_cap][2] of (i, j) in stacked-frame rows and columns; the first
+ * len_out[p] entries of pair p are its path, the others hold -1. path_cap must be at least the
+ * stacked length of max_len (ACOSS_E_ARG otherwise; no pair's path is longer). qmax_out, seg_out,
+ * oti_out may be NULL, len_out and path_out must not be; seg_out is acoss_crp_locate's and
+ * qmax_out acoss_crp_align's, bit for bit (same CRP kernels, same workspace). A stacked length
+ * above 65,535 returns ACOSS_E_SHAPE. */
+int acoss_crp_path(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                   int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                   float* qmax_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
+                   int32_t* path_out, void* hip_stream);
+/* the same on a given binary matrix (mirrors acoss_locate_crp, non-binary input refused alike):
+ * score_out float[1], seg_out int32[4] (may be NULL), len_out int32[1], path_out
+ * int32[path_cap][2]; path_cap below min(M, N) returns ACOSS_E_ARG, M or N above 65,535
+ * ACOSS_E_SHAPE. A matrix with fewer than 3 rows or columns has score 0 and an empty path. */
+int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext, float* score_out,
+                   int32_t* seg_out, int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream);
+
 /* acoss smith_waterman_constrained (A8, acoss/algorithms/utils/alignment_tools.py:25-46) on
  * a batch of binary matrices: matrix b is (rows[b] x cols[b]) uint8 at byte offset off[b]
  * of `mats`. score_out: double[n_mats]. Bit-exact float64 (same evaluation order). */
