@@ -200,29 +200,46 @@ def crp_params(m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5)
 # ----------------------------------------------------------------------------------------
 # Thin wrappers: inputs/outputs are torch CUDA tensors.
 # ----------------------------------------------------------------------------------------
-def crp_align(feats, track_off, track_len, max_len, pairs, params, qmax=True, dmax=False, oti=False):
-    """Batched Serra09/Chen path. feats (sum_n, 12) f32, track_off (T,) i64, track_len (T,) i32,
-    pairs (P, 2) i32 (query, reference) -> dict of device tensors."""
+def stacked_len(n, m=9, tau=1):
+    """essentia stackChromaFrames count (common.hpp stacked_len)."""
+    inc = m * tau
+    return 0 if n <= inc else (n - inc + tau - 1) // tau
+
+
+def _bank_args(feats, track_off, track_len, max_len, pairs, params):
+    """What acoss_crp_align, acoss_crp_locate and acoss_crp_path take first: (device tensors to keep
+    alive until the call is queued, P, the eight ctypes arguments up to params)."""
     torch = _torch()
-    lib = load_library()
     feats = _dev(feats, torch.float32)
     track_off = _dev(track_off, torch.int64)
     track_len = _dev(track_len, torch.int32)
     pairs, _ = _pairs_dev(pairs, int(track_len.shape[0]))
-    P = pairs.shape[0]
-    out = {}
-    q = torch.empty(P, dtype=torch.float32, device="cuda") if qmax else None
-    d = torch.empty(P, dtype=torch.float32, device="cuda") if dmax else None
-    o = torch.empty(P, dtype=torch.int32, device="cuda") if oti else None
-    rc = lib.acoss_crp_align(_ptr(feats), _ptr(track_off), _ptr(track_len), int(track_len.shape[0]), int(max_len),
-                             _ptr(pairs), int(P), ctypes.byref(params), _ptr(q), _ptr(d), _ptr(o), _stream())
+    P = int(pairs.shape[0])
+    lead = (_ptr(feats), _ptr(track_off), _ptr(track_len), int(track_len.shape[0]), int(max_len), _ptr(pairs), P,
+            ctypes.byref(params))
+    return (feats, track_off, track_len, pairs), P, lead
+
+
+def _matrix_args(C, gamma_open, gamma_ext):
+    """What the given-matrix entries take: (C on the device as uint8, M, N, gamma_open, gamma_ext, stream)."""
+    C = _dev(C, _torch().uint8)
+    return C, int(C.shape[0]), int(C.shape[1]), float(gamma_open), float(gamma_ext), _stream()
+
+
+def _empty(dtype, *shape):
+    torch = _torch()
+    return torch.empty(shape, dtype=getattr(torch, dtype), device="cuda")
+
+
+def crp_align(feats, track_off, track_len, max_len, pairs, params, qmax=True, dmax=False, oti=False):
+    """Batched Serra09/Chen path. feats (sum_n, 12) f32, track_off (T,) i64, track_len (T,) i32,
+    pairs (P, 2) i32 (query, reference) -> dict of device tensors."""
+    keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
+    want = (("qmax", qmax, "float32"), ("dmax", dmax, "float32"), ("oti", oti, "int32"))
+    out = {key: _empty(dtype, P) for key, on, dtype in want if on}
+    rc = load_library().acoss_crp_align(*lead, _ptr(out.get("qmax")), _ptr(out.get("dmax")), _ptr(out.get("oti")),
+                                        _stream())
     _check(rc, "acoss_crp_align")
-    if qmax:
-        out["qmax"] = q
-    if dmax:
-        out["dmax"] = d
-    if oti:
-        out["oti"] = o
     return out
 
 
@@ -233,14 +250,10 @@ def crp_pair(X, Y, params, dist=True):
     X = _dev(X, torch.float32)
     Y = _dev(Y, torch.float32)
     M, N = X.shape[0], Y.shape[0]
-    m, tau = params.m, params.tau
-    Mp = max(0, -(-(M - m * tau) // tau)) if M > m * tau else 0
-    Np = max(0, -(-(N - m * tau) // tau)) if N > m * tau else 0
-    D = torch.empty((Mp, Np), dtype=torch.float32, device="cuda") if dist else None
-    tr = torch.empty(Mp, dtype=torch.float32, device="cuda")
-    tc = torch.empty(Np, dtype=torch.float32, device="cuda")
-    C = torch.empty((Mp, Np), dtype=torch.uint8, device="cuda")
-    o = torch.empty(1, dtype=torch.int32, device="cuda")
+    Mp, Np = stacked_len(M, params.m, params.tau), stacked_len(N, params.m, params.tau)
+    D = _empty("float32", Mp, Np) if dist else None
+    tr, tc = _empty("float32", Mp), _empty("float32", Np)
+    C, o = _empty("uint8", Mp, Np), _empty("int32", 1)
     rc = lib.acoss_crp_pair(_ptr(X), M, _ptr(Y), N, ctypes.byref(params), _ptr(D), _ptr(tr), _ptr(tc), _ptr(C),
                             _ptr(o), _stream())
     _check(rc, "acoss_crp_pair")
@@ -249,12 +262,9 @@ def crp_pair(X, Y, params, dist=True):
 
 def align_crp(C, align=0, gamma_open=0.5, gamma_ext=0.5):
     """essentia CoverSongSimilarity(serra09|chen17, 'symmetric') on a binary (M, N) matrix."""
-    torch = _torch()
-    lib = load_library()
-    C = _dev(C, torch.uint8)
-    out = torch.empty(1, dtype=torch.float32, device="cuda")
-    rc = lib.acoss_align_crp(_ptr(C), int(C.shape[0]), int(C.shape[1]), int(align), float(gamma_open),
-                             float(gamma_ext), _ptr(out), _stream())
+    C, M, N, go, ge, stream = _matrix_args(C, gamma_open, gamma_ext)
+    out = _empty("float32", 1)
+    rc = load_library().acoss_align_crp(_ptr(C), M, N, int(align), go, ge, _ptr(out), stream)
     _check(rc, "acoss_align_crp")
     return out
 
@@ -263,32 +273,19 @@ def crp_locate(feats, track_off, track_len, max_len, pairs, params):
     """Batched Qmax with its location (acoss_crp_locate): inputs as crp_align. Returns device tensors
     {"qmax" (P,) f32, "seg" (P, 4) i32 = (i0, j0, i1, j1) in stacked-frame rows / columns, (-1, -1, -1, -1)
     where Qmax is 0, "oti" (P,) i32}."""
-    torch = _torch()
-    lib = load_library()
-    feats = _dev(feats, torch.float32)
-    track_off = _dev(track_off, torch.int64)
-    track_len = _dev(track_len, torch.int32)
-    pairs, _ = _pairs_dev(pairs, int(track_len.shape[0]))
-    P = pairs.shape[0]
-    q = torch.empty(P, dtype=torch.float32, device="cuda")
-    seg = torch.empty((P, 4), dtype=torch.int32, device="cuda")
-    o = torch.empty(P, dtype=torch.int32, device="cuda")
-    rc = lib.acoss_crp_locate(_ptr(feats), _ptr(track_off), _ptr(track_len), int(track_len.shape[0]), int(max_len),
-                              _ptr(pairs), int(P), ctypes.byref(params), _ptr(q), _ptr(seg), _ptr(o), _stream())
+    keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
+    out = {"qmax": _empty("float32", P), "seg": _empty("int32", P, 4), "oti": _empty("int32", P)}
+    rc = load_library().acoss_crp_locate(*lead, _ptr(out["qmax"]), _ptr(out["seg"]), _ptr(out["oti"]), _stream())
     _check(rc, "acoss_crp_locate")
-    return {"qmax": q, "seg": seg, "oti": o}
+    return out
 
 
 def locate_crp(C, gamma_open=0.5, gamma_ext=0.5):
     """Qmax of a binary (M, N) matrix and where it lies (acoss_locate_crp): (score (1,) f32,
     seg (4,) i32 = (i0, j0, i1, j1)) device tensors; the score is align_crp(C, 0, ...)'s."""
-    torch = _torch()
-    lib = load_library()
-    C = _dev(C, torch.uint8)
-    out = torch.empty(1, dtype=torch.float32, device="cuda")
-    seg = torch.empty(4, dtype=torch.int32, device="cuda")
-    rc = lib.acoss_locate_crp(_ptr(C), int(C.shape[0]), int(C.shape[1]), float(gamma_open), float(gamma_ext),
-                              _ptr(out), _ptr(seg), _stream())
+    C, M, N, go, ge, stream = _matrix_args(C, gamma_open, gamma_ext)
+    out, seg = _empty("float32", 1), _empty("int32", 4)
+    rc = load_library().acoss_locate_crp(_ptr(C), M, N, go, ge, _ptr(out), _ptr(seg), stream)
     _check(rc, "acoss_locate_crp")
     return out, seg
 
@@ -314,24 +311,17 @@ def crp_path(feats, track_off, track_len, max_len, pairs, params):
     library in chunks whose padded output stays near PATH_CHUNK_BYTES; each is compacted on the device."""
     torch = _torch()
     lib = load_library()
-    feats = _dev(feats, torch.float32)
-    track_off = _dev(track_off, torch.int64)
-    track_len = _dev(track_len, torch.int32)
-    pairs, _ = _pairs_dev(pairs, int(track_len.shape[0]))
-    P = pairs.shape[0]
-    m, tau = params.m, params.tau
-    cap = max(1, 0 if max_len <= m * tau else (int(max_len) - m * tau + tau - 1) // tau)
-    q = torch.empty(P, dtype=torch.float32, device="cuda")
-    seg = torch.empty((P, 4), dtype=torch.int32, device="cuda")
-    o = torch.empty(P, dtype=torch.int32, device="cuda")
-    lens = torch.empty(P, dtype=torch.int32, device="cuda")
+    keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
+    pairs = keep[3]
+    cap = max(1, stacked_len(int(max_len), params.m, params.tau))
+    q, seg, o = _empty("float32", P), _empty("int32", P, 4), _empty("int32", P)
+    lens = _empty("int32", P)
     chunk = max(1, PATH_CHUNK_BYTES // (8 * cap))
     parts = []
     for a in range(0, P, chunk):
         n = min(chunk, P - a)
         padded = torch.empty((n, cap, 2), dtype=torch.int32, device="cuda")
-        rc = lib.acoss_crp_path(_ptr(feats), _ptr(track_off), _ptr(track_len), int(track_len.shape[0]), int(max_len),
-                                _ptr(pairs[a:a + n]), int(n), ctypes.byref(params), _ptr(q[a:a + n]),
+        rc = lib.acoss_crp_path(*lead[:5], _ptr(pairs[a:a + n]), int(n), lead[7], _ptr(q[a:a + n]),
                                 _ptr(seg[a:a + n]), _ptr(o[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded),
                                 _stream())
         _check(rc, "acoss_crp_path")
@@ -346,16 +336,12 @@ def path_crp(C, gamma_open=0.5, gamma_ext=0.5, path_cap=None):
     """Qmax of a binary (M, N) matrix and its alignment path (acoss_path_crp): (score (1,) f32, seg (4,)
     i32, cells (len, 2) i32) device tensors; score and seg are locate_crp's. path_cap: entries of the
     padded buffer handed to the library, min(M, N) unless given (a smaller one is refused)."""
-    torch = _torch()
-    lib = load_library()
-    C = _dev(C, torch.uint8)
-    cap = max(1, min(int(C.shape[0]), int(C.shape[1]))) if path_cap is None else int(path_cap)
-    out = torch.empty(1, dtype=torch.float32, device="cuda")
-    seg = torch.empty(4, dtype=torch.int32, device="cuda")
-    n = torch.empty(1, dtype=torch.int32, device="cuda")
-    padded = torch.empty((max(1, cap), 2), dtype=torch.int32, device="cuda")
-    rc = lib.acoss_path_crp(_ptr(C), int(C.shape[0]), int(C.shape[1]), float(gamma_open), float(gamma_ext), _ptr(out),
-                            _ptr(seg), cap, _ptr(n), _ptr(padded), _stream())
+    C, M, N, go, ge, stream = _matrix_args(C, gamma_open, gamma_ext)
+    cap = max(1, min(M, N)) if path_cap is None else int(path_cap)
+    out, seg, n = _empty("float32", 1), _empty("int32", 4), _empty("int32", 1)
+    padded = _empty("int32", max(1, cap), 2)
+    rc = load_library().acoss_path_crp(_ptr(C), M, N, go, ge, _ptr(out), _ptr(seg), cap, _ptr(n), _ptr(padded),
+                                       stream)
     _check(rc, "acoss_path_crp")
     return out, seg, padded[:int(n.item())]
 

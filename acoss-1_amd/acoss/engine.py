@@ -10,13 +10,8 @@ overrides) with one batched call per pair chunk.
 import numpy as np
 
 from . import _lib
+from ._lib import stacked_len  # also this module's public name for it
 from .synthetic import pack
-
-
-def stacked_len(n, m=9, tau=1):
-    """essentia stackChromaFrames count (crp.hip stacked_len)."""
-    inc = m * tau
-    return 0 if n <= inc else (n - inc + tau - 1) // tau
 
 
 def segment_frames(seg, m, tau, factor, n_query, n_reference):
@@ -88,41 +83,34 @@ class ChromaBank:
                              % (short[:5], m, tau))
         return pairs
 
+    def _crp(self, fn, empty, pairs, crp, **want):
+        """The three scorers below: fn = the _lib function (want: its output switches); empty = (key,
+        shape, dtype name) of what it returns, for an empty pair list; crp = crp_params' arguments."""
+        torch = _lib._torch()
+        pairs = self._pairs(pairs, crp[0], crp[1])
+        if pairs is None:
+            return {k: torch.zeros(shape, dtype=getattr(torch, dt), device="cuda") for k, shape, dt in empty}
+        params = _lib.crp_params(*crp)
+        return fn(self.feats, self.off, self.len, self.max_len, pairs, params, **want)
+
+    _LOCATED = (("qmax", 0, "float32"), ("seg", (0, 4), "int32"), ("oti", 0, "int32"))
+
     def crp_align(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, qmax=True,
                   dmax=False, want_oti=False):
         """Serra09 (Qmax) / Chen (dmax) scores for (query, reference) pairs."""
-        torch = _lib._torch()
-        pairs = self._pairs(pairs, m, tau)
-        if pairs is None:
-            z = torch.zeros(0, dtype=torch.float32, device="cuda")
-            return {k: z for k, on in (("qmax", qmax), ("dmax", dmax), ("oti", want_oti)) if on}
-        params = _lib.crp_params(m, tau, kappa, oti, gamma_open, gamma_ext)
-        return _lib.crp_align(self.feats, self.off, self.len, self.max_len, pairs, params, qmax=qmax,
-                              dmax=dmax, oti=want_oti)
+        empty = [(k, 0, dt) for k, dt, on in (("qmax", "float32", qmax), ("dmax", "float32", dmax),
+                                              ("oti", "int32", want_oti)) if on]
+        return self._crp(_lib.crp_align, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext),
+                         qmax=qmax, dmax=dmax, oti=want_oti)
 
     def crp_locate(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5):
         """Qmax of (query, reference) pairs and where it lies: {"qmax", "seg" (P, 4), "oti"} device
         tensors (see _lib.crp_locate); the scores are crp_align's."""
-        torch = _lib._torch()
-        pairs = self._pairs(pairs, m, tau)
-        if pairs is None:
-            return {"qmax": torch.zeros(0, dtype=torch.float32, device="cuda"),
-                    "seg": torch.zeros((0, 4), dtype=torch.int32, device="cuda"),
-                    "oti": torch.zeros(0, dtype=torch.int32, device="cuda")}
-        params = _lib.crp_params(m, tau, kappa, oti, gamma_open, gamma_ext)
-        return _lib.crp_locate(self.feats, self.off, self.len, self.max_len, pairs, params)
+        return self._crp(_lib.crp_locate, self._LOCATED, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext))
 
     def crp_path(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5):
         """Qmax of (query, reference) pairs with the whole alignment path of each: {"qmax", "seg"
         (P, 4), "oti", "path_off" (P + 1,), "cells" (total, 2)} device tensors (see _lib.crp_path);
         scores and segments are crp_locate's."""
-        torch = _lib._torch()
-        pairs = self._pairs(pairs, m, tau)
-        if pairs is None:
-            return {"qmax": torch.zeros(0, dtype=torch.float32, device="cuda"),
-                    "seg": torch.zeros((0, 4), dtype=torch.int32, device="cuda"),
-                    "oti": torch.zeros(0, dtype=torch.int32, device="cuda"),
-                    "path_off": torch.zeros(1, dtype=torch.int64, device="cuda"),
-                    "cells": torch.zeros((0, 2), dtype=torch.int32, device="cuda")}
-        params = _lib.crp_params(m, tau, kappa, oti, gamma_open, gamma_ext)
-        return _lib.crp_path(self.feats, self.off, self.len, self.max_len, pairs, params)
+        empty = self._LOCATED + (("path_off", 1, "int64"), ("cells", (0, 2), "int32"))
+        return self._crp(_lib.crp_path, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext))

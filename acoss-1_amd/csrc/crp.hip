@@ -481,6 +481,21 @@ __global__ void k_pack_mask(const uint8_t* __restrict__ C, int M, int N, int ld,
 // --------------------------------------------------------------------------------------
 namespace {
 
+// The workspace slots of this file (the other files number their own).
+enum CrpSlot {
+  SLOT_TRACKS = 0,  // run_prep: the per-track tables of one call (TrackPrep)
+  SLOT_PLAN = 1,    // crp_plan: the per-pair tables of a DP batch and the key planes of its sub-batches
+  // acoss_crp_pair: the pair as a corpus of two tracks and a batch of one pair: packed features and
+  // the tables a caller of acoss_crp_align passes in
+  SLOT_PAIR = 2,
+  SLOT_ALIGN_CRP = 3,  // acoss_align_crp: the packed matrix (MatrixView) and the DP's band boundaries
+  // band-boundary records of the tracing DP, in a slot of their own (crp_plan's carving is the
+  // shipped DP's): acoss_crp_locate per pair of a DP batch, acoss_locate_crp after its MatrixView
+  SLOT_LOCATE = 22, SLOT_LOCATE_CRP = 23,
+  // the direction DP's plane, band-boundary records and end keys, likewise: acoss_crp_path, acoss_path_crp
+  SLOT_PATH = 24, SLOT_PATH_CRP = 25,
+};
+
 int check_params(const acoss_crp_params* P) {
   if (!P) {
     set_error("params is NULL");
@@ -511,7 +526,7 @@ int set_lds(K kernel, size_t bytes) {
   return ACOSS_OK;
 }
 
-// Per-track tables of one call, in workspace slot 0: prof (n_tracks x 12) | NX (n_tracks x ldn) |
+// Per-track tables of one call, in workspace slot SLOT_TRACKS: prof (n_tracks x 12) | NX (n_tracks x ldn) |
 // X2, the interleaved frame pairs of the split sweep (n_tracks x ldn x 24).
 struct TrackPrep {
   const float* feats;
@@ -527,7 +542,7 @@ int run_prep(const float* feats, const int64_t* off, const int32_t* len, int n_t
   // to 31 past the track's end (values unused: those rows are never stored)
   const int ldn = (int)align_up((size_t)max_len + 32, 64);
   const size_t base = align_up((size_t)n_tracks * 12 + (size_t)n_tracks * ldn, 64);
-  float* ws = static_cast<float*>(workspace(0, (base + (size_t)n_tracks * ldn * 24) * sizeof(float)));
+  float* ws = static_cast<float*>(workspace(SLOT_TRACKS, (base + (size_t)n_tracks * ldn * 24) * sizeof(float)));
   if (!ws) return ACOSS_E_HIP;
   *T = TrackPrep{feats, off, len, ws, ws + (size_t)n_tracks * 12, ws + base, ldn};
   if (max_len > 0) {
@@ -546,7 +561,7 @@ int run_prep(const float* feats, const int64_t* off, const int32_t* len, int n_t
 }
 
 // What one CRP call derives from (m, tau, longest track, pairs): which of the two paths runs, the
-// pitches its kernels index with, and workspace slot 1 carved to them. acoss_crp_align and
+// pitches its kernels index with, and workspace slot SLOT_PLAN carved to them. acoss_crp_align and
 // acoss_crp_pair both get it from crp_plan and their thresholds and CRP words from crp_masks, so
 // the single pair runs the batch's kernels on the batch's buffers (the read margins the split
 // kernels rely on included).
@@ -639,7 +654,7 @@ int crp_plan(int m, int tau, int max_len, int64_t n_pairs, hipStream_t s, CrpPla
   const char* e = getenv("ACOSS_SPLIT_STREAMS");
   const int v = e ? atoi(e) : 2;
   P.nbuf = !P.split ? 0 : (v < 1 ? 1 : (v > 3 ? 3 : v));
-  char* ws = static_cast<char*>(workspace(1, slot * nb_alloc + P.nbuf * sub_pair * P.sub + 8192));
+  char* ws = static_cast<char*>(workspace(SLOT_PLAN, slot * nb_alloc + P.nbuf * sub_pair * P.sub + 8192));
   if (!ws) return ACOSS_E_HIP;
   size_t o = 0;
   auto carve = [&](size_t bytes) {
@@ -733,17 +748,31 @@ int crp_masks(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int nb, c
   return ACOSS_OK;
 }
 
-}  // namespace
+// A packed cell of the tracing and direction DPs has 16 bits per coordinate: the longest stacked
+// length of a batch (N < 0) or the M x N of a given matrix.
+int check_cell_bits(int M, int N = -1) {
+  if (M <= kTraceMaxLen && N <= kTraceMaxLen) return ACOSS_OK;
+  if (N < 0)
+    set_error("stacked length %d above %d: a packed cell has 16 bits per coordinate", M, kTraceMaxLen);
+  else
+    set_error("matrix %d x %d above %d rows or columns: a packed cell has 16 bits per coordinate", M, N, kTraceMaxLen);
+  return ACOSS_E_SHAPE;
+}
 
-}  // namespace acoss
+const auto no_hook = [](auto&&...) { return ACOSS_OK; };
 
-using namespace acoss;
-
-extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, const int32_t* track_len,
-                               int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
-                               const acoss_crp_params* params, float* qmax_out, float* dmax_out, int32_t* oti_out,
-                               void* hip_stream) {
-  clear_error();
+// The batch driver under acoss_crp_align, acoss_crp_locate and acoss_crp_path: the checks the three
+// share, the plan, the per-track preparation, then DP batch after DP batch: crp_masks, the entry's
+// DP, the OTI copy.
+//   check()          the entry's own argument checks, after the shared ones (so an empty pair list
+//                    is answered first) and before anything is allocated;
+//   setup(C, nbd)    once the plan is known: the entry sizes and fetches its own workspace slot
+//                    and may lower the DP batch nbd below C.nb_alloc;
+//   dp(C, base, nb)  launches the entry's DP for pairs [base, base + nb) under its own phases.
+template <class Check, class Setup, class Dp>
+int crp_batches(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                hipStream_t s, int32_t* oti_out, Check check, Setup setup, Dp dp) {
   int rc = check_params(params);
   if (rc) return rc;
   if (n_pairs < 0 || n_tracks < 0 || max_len < 0) {
@@ -755,35 +784,136 @@ extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, con
     set_error("NULL input pointer");
     return ACOSS_E_ARG;
   }
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if ((rc = check())) return rc;
   CrpPlan C;
   if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, s, C))) return rc;
   TrackPrep T;
   prof_begin(PH_PREP, s);
   if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, C.m, C.tau, s, &T))) return rc;
   prof_end(PH_PREP, s);
-
-  const bool eqg = params->gamma_open == params->gamma_ext;
-  for (int64_t base = 0; base < n_pairs; base += C.nb_alloc) {
-    const int nb = (int)((n_pairs - base) < C.nb_alloc ? (n_pairs - base) : C.nb_alloc);
+  int64_t nbd = C.nb_alloc;
+  if ((rc = setup(C, nbd))) return rc;
+  for (int64_t base = 0; base < n_pairs; base += nbd) {
+    const int nb = (int)((n_pairs - base) < nbd ? (n_pairs - base) : nbd);
     if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
-    if (qmax_out) {
-      prof_begin(PH_DP_QMAX, s);
-      launch_dp(0, eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
-                   C.bnd_stride, qmax_out + base, s);
-      ACOSS_LAUNCH_CHECK();
-      prof_end(PH_DP_QMAX, s);
-    }
-    if (dmax_out) {
-      prof_begin(PH_DP_DMAX, s);
-      launch_dp(1, eqg, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, C.bnd,
-                   C.bnd_stride, dmax_out + base, s);
-      ACOSS_LAUNCH_CHECK();
-      prof_end(PH_DP_DMAX, s);
-    }
+    if ((rc = dp(C, base, nb))) return rc;
     if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
   }
   return ACOSS_OK;
+}
+
+// The direction plane of one DP batch stays under this many bytes (acoss_crp_path shrinks its DP
+// batch below crp_plan's where needed): 1 MB per pair at 2,000 frames still gives a launch of
+// about 4,000 waves.
+size_t path_plane_budget() {
+  size_t budget = (size_t)4 << 30;
+  if (const char* e = getenv("ACOSS_PATH_BYTES")) budget = strtoull(e, nullptr, 10);
+  return budget;
+}
+
+// acoss_crp_path's DP batch: crp_plan's unless its planes (pstride bytes per pair) would pass the
+// budget, and then batches of equal size: a last batch of a few pairs would be a launch that fills
+// no GPU.
+int64_t path_dp_batch(int64_t n_pairs, int64_t nb_alloc, int64_t pstride, size_t budget) {
+  int64_t nbp = (int64_t)(budget / (size_t)pstride);
+  if (nbp < 1) nbp = 1;
+  if (nbp > nb_alloc) nbp = nb_alloc;
+  const int64_t nbatches = (n_pairs + nbp - 1) / nbp;
+  return (n_pairs + nbatches - 1) / nbatches;
+}
+
+// A given M x N matrix as the DP takes it, in one workspace slot: the error flag at 0, the dims at
+// 64, one spare word at 128 (the path's end key), the mask words from 256, then the regions the
+// entry asked for, each aligned to 256 B.
+struct MatrixView {
+  int* d_err;
+  int2* d_dims;
+  uint32_t* d_end;
+  uint32_t* maskT;
+  int ld;
+  char* region[2];
+};
+
+int matrix_pitch(int N) { return (int)align_up((size_t)N, 8); }
+
+// Lays the slot out, uploads its header and packs crp into mask words (k_pack_mask raises the
+// error flag at an element above 1) on stream s.
+int pack_matrix(int slot, const uint8_t* crp, int M, int N, size_t bytes0, size_t bytes1, hipStream_t s,
+                MatrixView& V) {
+  const int ld = matrix_pitch(N);
+  const int nstrips = (M + 31) / 32;
+  const size_t mask_bytes = align_up(4 * (size_t)nstrips * ld, 256);
+  bytes0 = align_up(bytes0, 256);
+  char* ws = static_cast<char*>(workspace(slot, 256 + mask_bytes + bytes0 + align_up(bytes1, 256)));
+  if (!ws) return ACOSS_E_HIP;
+  V = MatrixView{reinterpret_cast<int*>(ws),
+                 reinterpret_cast<int2*>(ws + 64),
+                 reinterpret_cast<uint32_t*>(ws + 128),
+                 reinterpret_cast<uint32_t*>(ws + 256),
+                 ld,
+                 {ws + 256 + mask_bytes, ws + 256 + mask_bytes + bytes0}};
+  const int h_hdr[4] = {0, 0, M, N};  // err, pad, dims
+  ACOSS_HIP_CHECK(hipMemcpy(V.d_err, h_hdr, 8, hipMemcpyHostToDevice));
+  ACOSS_HIP_CHECK(hipMemcpy(V.d_dims, h_hdr + 2, 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, V.maskT, V.d_err);
+  ACOSS_LAUNCH_CHECK();
+  return ACOSS_OK;
+}
+
+// After the entry's launches: waits for them and refuses a matrix that k_pack_mask flagged.
+int matrix_finish(const MatrixView& V, hipStream_t s) {
+  int h_err = 0;
+  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, V.d_err, 4, hipMemcpyDeviceToHost, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  if (h_err) {
+    set_error("CoverSongSimilarity: non-binary elements found in the input similarity matrix");
+    return ACOSS_E_NONBINARY;
+  }
+  return ACOSS_OK;
+}
+
+// The answer for a matrix without rows or columns: score 0, no segment, an empty path (seg, len
+// and path where the entry has them).
+int empty_matrix_answer(float* score_out, int32_t* seg_out, int32_t* len_out, int32_t* path_out, int32_t path_cap,
+                        hipStream_t s) {
+  const float z = 0.0f;
+  const int32_t none[4] = {-1, -1, -1, -1};
+  const int32_t zero = 0;
+  if (path_out && path_cap > 0) ACOSS_HIP_CHECK(hipMemsetAsync(path_out, 0xff, 8 * (size_t)path_cap, s));
+  ACOSS_HIP_CHECK(hipMemcpyAsync(score_out, &z, 4, hipMemcpyHostToDevice, s));
+  if (seg_out) ACOSS_HIP_CHECK(hipMemcpyAsync(seg_out, none, sizeof(none), hipMemcpyHostToDevice, s));
+  if (len_out) ACOSS_HIP_CHECK(hipMemcpyAsync(len_out, &zero, 4, hipMemcpyHostToDevice, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  return ACOSS_OK;
+}
+
+}  // namespace
+
+}  // namespace acoss
+
+using namespace acoss;
+
+extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                               int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                               const acoss_crp_params* params, float* qmax_out, float* dmax_out, int32_t* oti_out,
+                               void* hip_stream) {
+  clear_error();
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  float* const out[2] = {qmax_out, dmax_out};  // by launch_dp's align: 0 = Qmax, 1 = dmax
+  const int phase[2] = {PH_DP_QMAX, PH_DP_DMAX};
+  return crp_batches(
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out, no_hook, no_hook,
+      [&](const CrpPlan& C, int64_t base, int nb) {
+        for (int align = 0; align < 2; ++align) {
+          if (!out[align]) continue;
+          prof_begin(phase[align], s);
+          launch_dp(align, params->gamma_open == params->gamma_ext, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims,
+                    params->gamma_open, params->gamma_ext, C.bnd, C.bnd_stride, out[align] + base, s);
+          ACOSS_LAUNCH_CHECK();
+          prof_end(phase[align], s);
+        }
+        return ACOSS_OK;
+      });
 }
 
 extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params* params,
@@ -799,13 +929,11 @@ extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t
     return ACOSS_E_SHAPE;
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  // the pair as a corpus of two tracks and a batch of one pair: packed features and the tables a
-  // caller of acoss_crp_align passes in, in workspace slot 2
   const int max_len = M > N ? M : N;
   CrpPlan C;
   if ((rc = crp_plan(m, tau, max_len, 1, s, C))) return rc;
   const size_t fbytes = align_up((size_t)(M + N) * 12 * 4, 256);
-  char* ws = static_cast<char*>(workspace(2, fbytes + 256));
+  char* ws = static_cast<char*>(workspace(SLOT_PAIR, fbytes + 256));
   if (!ws) return ACOSS_E_HIP;
   float* f = reinterpret_cast<float*>(ws);
   char* tab = ws + fbytes;
@@ -848,37 +976,15 @@ extern "C" int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t
     return ACOSS_E_ARG;
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  if (M == 0 || N == 0) {
-    const float z = 0.0f;
-    ACOSS_HIP_CHECK(hipMemcpyAsync(score_out, &z, 4, hipMemcpyHostToDevice, s));
-    ACOSS_HIP_CHECK(hipStreamSynchronize(s));
-    return ACOSS_OK;
-  }
-  const int ld = (int)align_up((size_t)N, 8);
-  const int nstrips = (M + 31) / 32, nbands = (M + 2047) / 2048;
-  const size_t bytes = 256 + 4 * (size_t)nstrips * ld + 16 * (size_t)nbands * ld;
-  char* ws = static_cast<char*>(workspace(3, bytes));
-  if (!ws) return ACOSS_E_HIP;
-  int* d_err = reinterpret_cast<int*>(ws);
-  int2* d_dims = reinterpret_cast<int2*>(ws + 64);
-  uint32_t* maskT = reinterpret_cast<uint32_t*>(ws + 256);
-  float4* bnd = reinterpret_cast<float4*>(ws + 256 + 4 * (size_t)nstrips * ld);
-  const int h_hdr[4] = {0, 0, M, N};  // err, pad, dims
-  ACOSS_HIP_CHECK(hipMemcpy(d_err, h_hdr, 8, hipMemcpyHostToDevice));
-  ACOSS_HIP_CHECK(hipMemcpy(d_dims, h_hdr + 2, 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, maskT, d_err);
+  if (M == 0 || N == 0) return empty_matrix_answer(score_out, nullptr, nullptr, nullptr, 0, s);
+  int rc;
+  MatrixView V;
+  const size_t bnd_bytes = 16 * (size_t)((M + 2047) / 2048) * matrix_pitch(N);
+  if ((rc = pack_matrix(SLOT_ALIGN_CRP, crp, M, N, bnd_bytes, 0, s, V))) return rc;
+  launch_dp(align, gamma_open == gamma_ext, 1, M, V.maskT, 0, V.ld, V.d_dims, gamma_open, gamma_ext,
+            reinterpret_cast<float4*>(V.region[0]), 0, score_out, s);
   ACOSS_LAUNCH_CHECK();
-  const bool eqg = gamma_open == gamma_ext;
-  launch_dp(align, eqg, 1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, s);
-  ACOSS_LAUNCH_CHECK();
-  int h_err = 0;
-  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));
-  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
-  if (h_err) {
-    set_error("CoverSongSimilarity: non-binary elements found in the input similarity matrix");
-    return ACOSS_E_NONBINARY;
-  }
-  return ACOSS_OK;
+  return matrix_finish(V, s);
 }
 
 extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, const int32_t* track_len,
@@ -886,46 +992,31 @@ extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, co
                                 const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                                 void* hip_stream) {
   clear_error();
-  int rc = check_params(params);
-  if (rc) return rc;
-  if (n_pairs < 0 || n_tracks < 0 || max_len < 0) {
-    set_error("negative size");
-    return ACOSS_E_ARG;
-  }
-  if (n_pairs == 0) return ACOSS_OK;
-  if (!feats || !track_off || !track_len || !pairs || !seg_out) {
-    set_error("NULL input pointer or seg_out");
-    return ACOSS_E_ARG;
-  }
-  if (stacked_len(max_len, params->m, params->tau) > kTraceMaxLen) {
-    set_error("stacked length %d above %d: a packed cell has 16 bits per coordinate",
-              stacked_len(max_len, params->m, params->tau), kTraceMaxLen);
-    return ACOSS_E_SHAPE;
-  }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  CrpPlan C;
-  if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, s, C))) return rc;
-  TrackPrep T;
-  prof_begin(PH_PREP, s);
-  if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, C.m, C.tau, s, &T))) return rc;
-  prof_end(PH_PREP, s);
-  // band-boundary records of the tracing DP, in a slot of their own (crp_plan's carving is the
-  // shipped DP's)
-  const int64_t tstride = trace_bnd_records(C.L, C.ld);
-  void* tb = workspace(22, kTraceRecBytes * (size_t)tstride * (size_t)C.nb_alloc);
-  if (!tb) return ACOSS_E_HIP;
-
-  for (int64_t base = 0; base < n_pairs; base += C.nb_alloc) {
-    const int nb = (int)((n_pairs - base) < C.nb_alloc ? (n_pairs - base) : C.nb_alloc);
-    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
-    prof_begin(PH_DP_TRACE, s);
-    launch_trace(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, tb, tstride,
-                 qmax_out ? qmax_out + base : nullptr, seg_out + 4 * base, s);
-    ACOSS_LAUNCH_CHECK();
-    prof_end(PH_DP_TRACE, s);
-    if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
-  }
-  return ACOSS_OK;
+  void* tb = nullptr;  // band-boundary records of the tracing DP, tstride per pair
+  int64_t tstride = 0;
+  return crp_batches(
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out,
+      [&] {
+        if (!seg_out) {
+          set_error("seg_out is NULL");
+          return ACOSS_E_ARG;
+        }
+        return check_cell_bits(stacked_len(max_len, params->m, params->tau));
+      },
+      [&](const CrpPlan& C, int64_t& nbd) {
+        tstride = trace_bnd_records(C.L, C.ld);
+        tb = workspace(SLOT_LOCATE, kTraceRecBytes * (size_t)tstride * (size_t)nbd);
+        return tb ? ACOSS_OK : ACOSS_E_HIP;
+      },
+      [&](const CrpPlan& C, int64_t base, int nb) {
+        prof_begin(PH_DP_TRACE, s);
+        launch_trace(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, tb, tstride,
+                     qmax_out ? qmax_out + base : nullptr, seg_out + 4 * base, s);
+        ACOSS_LAUNCH_CHECK();
+        prof_end(PH_DP_TRACE, s);
+        return ACOSS_OK;
+      });
 }
 
 extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
@@ -935,53 +1026,16 @@ extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float 
     set_error("bad arguments to acoss_locate_crp");
     return ACOSS_E_ARG;
   }
-  if (M > kTraceMaxLen || N > kTraceMaxLen) {
-    set_error("matrix %d x %d above %d rows or columns: a packed cell has 16 bits per coordinate", M, N, kTraceMaxLen);
-    return ACOSS_E_SHAPE;
-  }
+  int rc;
+  if ((rc = check_cell_bits(M, N))) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  if (M == 0 || N == 0) {
-    const float z = 0.0f;
-    const int32_t none[4] = {-1, -1, -1, -1};
-    ACOSS_HIP_CHECK(hipMemcpyAsync(score_out, &z, 4, hipMemcpyHostToDevice, s));
-    ACOSS_HIP_CHECK(hipMemcpyAsync(seg_out, none, sizeof(none), hipMemcpyHostToDevice, s));
-    ACOSS_HIP_CHECK(hipStreamSynchronize(s));
-    return ACOSS_OK;
-  }
-  const int ld = (int)align_up((size_t)N, 8);
-  const int nstrips = (M + 31) / 32;
-  const int64_t trecs = trace_bnd_records(M, ld);
-  const size_t mask_bytes = align_up(4 * (size_t)nstrips * ld, 256);
-  char* ws = static_cast<char*>(workspace(23, 256 + mask_bytes + kTraceRecBytes * (size_t)trecs));
-  if (!ws) return ACOSS_E_HIP;
-  int* d_err = reinterpret_cast<int*>(ws);
-  int2* d_dims = reinterpret_cast<int2*>(ws + 64);
-  uint32_t* maskT = reinterpret_cast<uint32_t*>(ws + 256);
-  void* bnd = ws + 256 + mask_bytes;
-  const int h_hdr[4] = {0, 0, M, N};  // err, pad, dims
-  ACOSS_HIP_CHECK(hipMemcpy(d_err, h_hdr, 8, hipMemcpyHostToDevice));
-  ACOSS_HIP_CHECK(hipMemcpy(d_dims, h_hdr + 2, 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, maskT, d_err);
+  if (M == 0 || N == 0) return empty_matrix_answer(score_out, seg_out, nullptr, nullptr, 0, s);
+  MatrixView V;
+  const size_t bnd_bytes = kTraceRecBytes * (size_t)trace_bnd_records(M, matrix_pitch(N));
+  if ((rc = pack_matrix(SLOT_LOCATE_CRP, crp, M, N, bnd_bytes, 0, s, V))) return rc;
+  launch_trace(1, M, V.maskT, 0, V.ld, V.d_dims, gamma_open, gamma_ext, V.region[0], 0, score_out, seg_out, s);
   ACOSS_LAUNCH_CHECK();
-  launch_trace(1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, score_out, seg_out, s);
-  ACOSS_LAUNCH_CHECK();
-  int h_err = 0;
-  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));
-  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
-  if (h_err) {
-    set_error("CoverSongSimilarity: non-binary elements found in the input similarity matrix");
-    return ACOSS_E_NONBINARY;
-  }
-  return ACOSS_OK;
-}
-
-// The direction plane of one DP batch stays under this many bytes (acoss_crp_path shrinks its DP
-// batch below crp_plan's where needed): 1 MB per pair at 2,000 frames still gives a launch of
-// about 4,000 waves.
-static size_t path_plane_budget() {
-  size_t budget = (size_t)4 << 30;
-  if (const char* e = getenv("ACOSS_PATH_BYTES")) budget = strtoull(e, nullptr, 10);
-  return budget;
+  return matrix_finish(V, s);
 }
 
 extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, const int32_t* track_len,
@@ -989,67 +1043,57 @@ extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, cons
                               const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                               int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
   clear_error();
-  int rc = check_params(params);
-  if (rc) return rc;
-  if (n_pairs < 0 || n_tracks < 0 || max_len < 0 || path_cap < 0) {
+  if (path_cap < 0) {
     set_error("negative size");
     return ACOSS_E_ARG;
   }
-  if (n_pairs == 0) return ACOSS_OK;
-  if (!feats || !track_off || !track_len || !pairs || !len_out || !path_out) {
-    set_error("NULL input pointer, len_out or path_out");
-    return ACOSS_E_ARG;
-  }
-  const int Lmax = stacked_len(max_len, params->m, params->tau);
-  if (Lmax > kTraceMaxLen) {
-    set_error("stacked length %d above %d: a packed cell has 16 bits per coordinate", Lmax, kTraceMaxLen);
-    return ACOSS_E_SHAPE;
-  }
-  if (path_cap < Lmax) {
-    set_error("path_cap %d below the longest stacked length %d: a path may have that many cells", path_cap, Lmax);
-    return ACOSS_E_ARG;
-  }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  CrpPlan C;
-  if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, s, C))) return rc;
-  TrackPrep T;
-  prof_begin(PH_PREP, s);
-  if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, C.m, C.tau, s, &T))) return rc;
-  prof_end(PH_PREP, s);
-  // the direction DP's plane, band-boundary records and end keys in a slot of their own; the DP
-  // batch is crp_plan's unless its planes would pass the budget
-  const int64_t pstride = (int64_t)align_up((size_t)dir_plane_bytes(C.L, C.ld), 256);
-  const int64_t bstride = trace_bnd_records(C.L, C.ld);
-  int64_t nbp = (int64_t)(path_plane_budget() / (size_t)pstride);
-  if (nbp < 1) nbp = 1;
-  if (nbp > C.nb_alloc) nbp = C.nb_alloc;
-  // batches of equal size: a last batch of a few pairs would be a launch that fills no GPU
-  const int64_t nbatches = (n_pairs + nbp - 1) / nbp;
-  nbp = (n_pairs + nbatches - 1) / nbatches;
-  const size_t plane_bytes = (size_t)pstride * (size_t)nbp;
-  const size_t bnd_bytes = align_up(sizeof(float4) * (size_t)bstride * (size_t)nbp, 256);
-  char* ws = static_cast<char*>(workspace(24, plane_bytes + bnd_bytes + 4 * (size_t)nbp));
-  if (!ws) return ACOSS_E_HIP;
-  uint8_t* plane = reinterpret_cast<uint8_t*>(ws);
-  float4* bnd = reinterpret_cast<float4*>(ws + plane_bytes);
-  uint32_t* endkey = reinterpret_cast<uint32_t*>(ws + plane_bytes + bnd_bytes);
-
-  for (int64_t base = 0; base < n_pairs; base += nbp) {
-    const int nb = (int)((n_pairs - base) < nbp ? (n_pairs - base) : nbp);
-    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
-    prof_begin(PH_DP_DIR, s);
-    launch_dir(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, bnd, bstride,
-               plane, pstride, endkey, qmax_out ? qmax_out + base : nullptr, s);
-    ACOSS_LAUNCH_CHECK();
-    prof_end(PH_DP_DIR, s);
-    prof_begin(PH_BACKTRACK, s);
-    launch_backtrack(nb, plane, pstride, C.ld, C.dims, endkey, path_cap, seg_out ? seg_out + 4 * base : nullptr,
-                     len_out + base, path_out + 2 * (size_t)path_cap * (size_t)base, s);
-    ACOSS_LAUNCH_CHECK();
-    prof_end(PH_BACKTRACK, s);
-    if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
-  }
-  return ACOSS_OK;
+  uint8_t* plane = nullptr;  // per pair of a DP batch: the direction plane (pstride bytes), the
+  float4* bnd = nullptr;     // band-boundary records (bstride) and the end key
+  uint32_t* endkey = nullptr;
+  int64_t pstride = 0, bstride = 0;
+  return crp_batches(
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out,
+      [&] {
+        if (!len_out || !path_out) {
+          set_error("len_out or path_out is NULL");
+          return ACOSS_E_ARG;
+        }
+        const int Lmax = stacked_len(max_len, params->m, params->tau);
+        if (int rc = check_cell_bits(Lmax)) return rc;
+        if (path_cap < Lmax) {
+          set_error("path_cap %d below the longest stacked length %d: a path may have that many cells", path_cap,
+                    Lmax);
+          return ACOSS_E_ARG;
+        }
+        return ACOSS_OK;
+      },
+      [&](const CrpPlan& C, int64_t& nbd) {
+        pstride = (int64_t)align_up((size_t)dir_plane_bytes(C.L, C.ld), 256);
+        bstride = trace_bnd_records(C.L, C.ld);
+        nbd = path_dp_batch(n_pairs, C.nb_alloc, pstride, path_plane_budget());
+        const size_t plane_bytes = (size_t)pstride * (size_t)nbd;
+        const size_t bnd_bytes = align_up(sizeof(float4) * (size_t)bstride * (size_t)nbd, 256);
+        char* ws = static_cast<char*>(workspace(SLOT_PATH, plane_bytes + bnd_bytes + 4 * (size_t)nbd));
+        if (!ws) return ACOSS_E_HIP;
+        plane = reinterpret_cast<uint8_t*>(ws);
+        bnd = reinterpret_cast<float4*>(ws + plane_bytes);
+        endkey = reinterpret_cast<uint32_t*>(ws + plane_bytes + bnd_bytes);
+        return ACOSS_OK;
+      },
+      [&](const CrpPlan& C, int64_t base, int nb) {
+        prof_begin(PH_DP_DIR, s);
+        launch_dir(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, bnd, bstride,
+                   plane, pstride, endkey, qmax_out ? qmax_out + base : nullptr, s);
+        ACOSS_LAUNCH_CHECK();
+        prof_end(PH_DP_DIR, s);
+        prof_begin(PH_BACKTRACK, s);
+        launch_backtrack(nb, plane, pstride, C.ld, C.dims, endkey, path_cap, seg_out ? seg_out + 4 * base : nullptr,
+                         len_out + base, path_out + 2 * (size_t)path_cap * (size_t)base, s);
+        ACOSS_LAUNCH_CHECK();
+        prof_end(PH_BACKTRACK, s);
+        return ACOSS_OK;
+      });
 }
 
 extern "C" int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
@@ -1060,54 +1104,25 @@ extern "C" int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float ga
     set_error("bad arguments to acoss_path_crp");
     return ACOSS_E_ARG;
   }
-  if (M > kTraceMaxLen || N > kTraceMaxLen) {
-    set_error("matrix %d x %d above %d rows or columns: a packed cell has 16 bits per coordinate", M, N, kTraceMaxLen);
-    return ACOSS_E_SHAPE;
-  }
+  int rc;
+  if ((rc = check_cell_bits(M, N))) return rc;
   if (path_cap < (M < N ? M : N)) {
     set_error("path_cap %d below min(M, N) = %d: a path may have that many cells", path_cap, M < N ? M : N);
     return ACOSS_E_ARG;
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  if (M == 0 || N == 0) {
-    if (path_cap > 0) ACOSS_HIP_CHECK(hipMemsetAsync(path_out, 0xff, 8 * (size_t)path_cap, s));
-    const float z = 0.0f;
-    const int32_t none[4] = {-1, -1, -1, -1};
-    const int32_t zero = 0;
-    ACOSS_HIP_CHECK(hipMemcpyAsync(score_out, &z, 4, hipMemcpyHostToDevice, s));
-    if (seg_out) ACOSS_HIP_CHECK(hipMemcpyAsync(seg_out, none, sizeof(none), hipMemcpyHostToDevice, s));
-    ACOSS_HIP_CHECK(hipMemcpyAsync(len_out, &zero, 4, hipMemcpyHostToDevice, s));
-    ACOSS_HIP_CHECK(hipStreamSynchronize(s));
-    return ACOSS_OK;
-  }
-  const int ld = (int)align_up((size_t)N, 8);
-  const int nstrips = (M + 31) / 32;
-  const size_t mask_bytes = align_up(4 * (size_t)nstrips * ld, 256);
-  const size_t bnd_bytes = align_up(sizeof(float4) * (size_t)trace_bnd_records(M, ld), 256);
-  const size_t plane_bytes = (size_t)dir_plane_bytes(M, ld);
-  char* ws = static_cast<char*>(workspace(25, 256 + mask_bytes + bnd_bytes + plane_bytes));
-  if (!ws) return ACOSS_E_HIP;
-  int* d_err = reinterpret_cast<int*>(ws);
-  int2* d_dims = reinterpret_cast<int2*>(ws + 64);
-  uint32_t* d_end = reinterpret_cast<uint32_t*>(ws + 128);
-  uint32_t* maskT = reinterpret_cast<uint32_t*>(ws + 256);
-  float4* bnd = reinterpret_cast<float4*>(ws + 256 + mask_bytes);
-  uint8_t* plane = reinterpret_cast<uint8_t*>(ws + 256 + mask_bytes + bnd_bytes);
-  const int h_hdr[4] = {0, 0, M, N};  // err, pad, dims
-  ACOSS_HIP_CHECK(hipMemcpy(d_err, h_hdr, 8, hipMemcpyHostToDevice));
-  ACOSS_HIP_CHECK(hipMemcpy(d_dims, h_hdr + 2, 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_pack_mask, dim3((N + 255) / 256, nstrips), dim3(256), 0, s, crp, M, N, ld, maskT, d_err);
+  if (M == 0 || N == 0) return empty_matrix_answer(score_out, seg_out, len_out, path_out, path_cap, s);
+  MatrixView V;
+  const int ld = matrix_pitch(N);
+  if ((rc = pack_matrix(SLOT_PATH_CRP, crp, M, N, sizeof(float4) * (size_t)trace_bnd_records(M, ld),
+                        (size_t)dir_plane_bytes(M, ld), s, V)))
+    return rc;
+  uint8_t* plane = reinterpret_cast<uint8_t*>(V.region[1]);
+  launch_dir(1, M, V.maskT, 0, ld, V.d_dims, gamma_open, gamma_ext, reinterpret_cast<float4*>(V.region[0]), 0, plane,
+             0, V.d_end, score_out, s);
   ACOSS_LAUNCH_CHECK();
-  launch_dir(1, M, maskT, 0, ld, d_dims, gamma_open, gamma_ext, bnd, 0, plane, 0, d_end, score_out, s);
+  launch_backtrack(1, plane, 0, ld, V.d_dims, V.d_end, path_cap, seg_out, len_out, path_out, s);
   ACOSS_LAUNCH_CHECK();
-  launch_backtrack(1, plane, 0, ld, d_dims, d_end, path_cap, seg_out, len_out, path_out, s);
-  ACOSS_LAUNCH_CHECK();
-  int h_err = 0;
-  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));
-  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
-  if (h_err) {
-    set_error("CoverSongSimilarity: non-binary elements found in the input similarity matrix");
-    return ACOSS_E_NONBINARY;
-  }
-  return ACOSS_OK;
+  return matrix_finish(V, s);
 }
+

@@ -28,6 +28,7 @@
 //                            for acoss_crp_path / acoss_path_crp
 // launch_dp, launch_trace and launch_dir choose among them.
 #include <cstdlib>
+#include <type_traits>
 
 #include "crp_internal.hpp"
 
@@ -982,23 +983,13 @@ void launch_dp_a(bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride
 // The tracing DP (k_crp_dp_trace): R = 8 takes the CRPs of at most 512 rows, R = 16 the longer
 // ones; a batch whose longest CRP has more than 512 rows gets both launches and each wave keeps
 // the pairs of its own R. The exact-halves select (EQG) under the fast DP's condition only. The
-// direction DP (k_crp_dp_dir) is launched the same way.
-
-template <int R>
-void launch_trace_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
-                    float go, float ge, TraceRec* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
+// direction DP (k_crp_dp_dir) is launched the same way: launch(R as a type, halves, row_lo, row_hi)
+// names the kernel.
+template <class Launch>
+void launch_by_rows(int L, float go, float ge, Launch launch) {
   const bool halves = go == ge && half_integer_gamma(go);
-  hipLaunchKernelGGL((halves ? k_crp_dp_trace<true, R> : k_crp_dp_trace<false, R>), dim3(nb), dim3(64), 0, s, maskT,
-                     mstride, ld, dims, row_lo, row_hi, go, ge, bnd, bstride, qmax, seg);
-}
-
-template <int R>
-void launch_dir_r(int nb, int row_lo, int row_hi, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
-                  float go, float ge, float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey,
-                  float* qmax, hipStream_t s) {
-  const bool halves = go == ge && half_integer_gamma(go);
-  hipLaunchKernelGGL((halves ? k_crp_dp_dir<true, R> : k_crp_dp_dir<false, R>), dim3(nb), dim3(64), 0, s, maskT,
-                     mstride, ld, dims, row_lo, row_hi, go, ge, bnd, bstride, plane, pstride, endkey, qmax);
+  launch(std::integral_constant<int, 8>{}, halves, -1, kTraceShortRows);
+  if (L > kTraceShortRows) launch(std::integral_constant<int, 16>{}, halves, kTraceShortRows, INT32_MAX);
 }
 
 }  // namespace
@@ -1017,10 +1008,11 @@ int64_t trace_bnd_records(int L, int ld) {  // per pair: ceil(L / (64 R)) * ld
 
 void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
                   void* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
-  TraceRec* tb = static_cast<TraceRec*>(bnd);
-  launch_trace_r<8>(nb, -1, kTraceShortRows, maskT, mstride, ld, dims, go, ge, tb, bstride, qmax, seg, s);
-  if (L > kTraceShortRows)
-    launch_trace_r<16>(nb, kTraceShortRows, INT32_MAX, maskT, mstride, ld, dims, go, ge, tb, bstride, qmax, seg, s);
+  launch_by_rows(L, go, ge, [&](auto r, bool halves, int row_lo, int row_hi) {
+    constexpr int R = decltype(r)::value;
+    hipLaunchKernelGGL((halves ? k_crp_dp_trace<true, R> : k_crp_dp_trace<false, R>), dim3(nb), dim3(64), 0, s, maskT,
+                       mstride, ld, dims, row_lo, row_hi, go, ge, static_cast<TraceRec*>(bnd), bstride, qmax, seg);
+  });
 }
 
 // per pair: ceil(L / 16) row groups of ld 32-bit words; the 16-bit words of the 8-row groups of a
@@ -1030,11 +1022,11 @@ int64_t dir_plane_bytes(int L, int ld) { return (int64_t)((L + 15) / 16) * ld * 
 void launch_dir(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
                 float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey, float* qmax,
                 hipStream_t s) {
-  launch_dir_r<8>(nb, -1, kTraceShortRows, maskT, mstride, ld, dims, go, ge, bnd, bstride, plane, pstride, endkey,
-                  qmax, s);
-  if (L > kTraceShortRows)
-    launch_dir_r<16>(nb, kTraceShortRows, INT32_MAX, maskT, mstride, ld, dims, go, ge, bnd, bstride, plane, pstride,
-                     endkey, qmax, s);
+  launch_by_rows(L, go, ge, [&](auto r, bool halves, int row_lo, int row_hi) {
+    constexpr int R = decltype(r)::value;
+    hipLaunchKernelGGL((halves ? k_crp_dp_dir<true, R> : k_crp_dp_dir<false, R>), dim3(nb), dim3(64), 0, s, maskT,
+                       mstride, ld, dims, row_lo, row_hi, go, ge, bnd, bstride, plane, pstride, endkey, qmax);
+  });
 }
 
 void launch_backtrack(int nb, const uint8_t* plane, int64_t pstride, int ld, const int2* dims, const uint32_t* endkey,

@@ -52,6 +52,21 @@ def test_crp_align_batch_matches_oracle():
     np.testing.assert_array_equal(got["dmax"].cpu().numpy(), d)
 
 
+def test_crp_align_small_dp_batches(monkeypatch):
+    """DP batches of 7 pairs (40 launches, the last of 3 pairs) with every output on give what one
+    batch gives: each output is offset per batch."""
+    tracks, _ = synthetic.make_corpus("covers80", frames=300, seed=7)
+    feats, off, lens = synthetic.pack(tracks[:24])
+    pairs = np.array([(i, j) for i in range(24) for j in range(i + 1, 24)], np.int32)
+    P = _lib.crp_params()
+    one = _lib.crp_align(feats, off, lens, int(lens.max()), pairs, P, qmax=True, dmax=True, oti=True)
+    monkeypatch.setenv("ACOSS_BATCH_PAIRS", "7")
+    many = _lib.crp_align(feats, off, lens, int(lens.max()), pairs, P, qmax=True, dmax=True, oti=True)
+    assert sorted(many) == ["dmax", "oti", "qmax"]
+    for key in ("qmax", "dmax", "oti"):
+        np.testing.assert_array_equal(many[key].cpu().numpy(), one[key].cpu().numpy(), err_msg=key)
+
+
 @pytest.mark.parametrize("M,N,go,ge,align", [(5, 5, 0.5, 0.5, 0), (300, 200, 0.5, 0.5, 0), (300, 200, 0.5, 0.5, 1),
                                              (2100, 90, 0.5, 0.5, 0), (2100, 90, 0.5, 0.5, 1),
                                              (4200, 70, 0.7, 0.3, 0), (4200, 70, 0.7, 0.3, 1),

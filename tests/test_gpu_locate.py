@@ -74,6 +74,20 @@ def test_crp_locate_batch(covers24):
     assert (seg[:, 0] >= 0).any()
 
 
+def test_crp_locate_small_dp_batches(covers24, monkeypatch):
+    """DP batches of 7 pairs (40 launches, the last of 3 pairs) give what one batch gives: the
+    boundary records are reused and the outputs offset per batch."""
+    tracks, pairs = covers24
+    feats, off, lens = synthetic.pack(tracks)
+    P = _lib.crp_params()
+    one = _lib.crp_locate(feats, off, lens, int(lens.max()), pairs, P)
+    monkeypatch.setenv("ACOSS_BATCH_PAIRS", "7")
+    many = _lib.crp_locate(feats, off, lens, int(lens.max()), pairs, P)
+    for key in ("qmax", "seg", "oti"):
+        np.testing.assert_array_equal(many[key].cpu().numpy(), one[key].cpu().numpy(), err_msg=key)
+    assert (one["seg"].cpu().numpy() != -1).any()
+
+
 def test_crp_locate_ragged_batch():
     """Lengths 37 .. 1100 in one launch: both rows-per-lane kernels (CRPs of at most 512 rows and
     longer ones), two bands at 16 rows per lane, mixed dims, and silences (huge tie groups)."""

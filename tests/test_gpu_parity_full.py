@@ -94,6 +94,31 @@ def test_batching_branches_ragged(monkeypatch, env):
     np.testing.assert_array_equal(out["dmax"].cpu().numpy(), od)
 
 
+def test_bank_scorers_on_an_empty_pair_list():
+    """No pairs: every scorer returns its documented keys with a leading dimension of 0, the
+    trailing shapes and the dtypes of a non-empty call, and path_off == [0]."""
+    import torch
+    from acoss.engine import ChromaBank
+    rng = np.random.default_rng(3)
+    bank = ChromaBank([synthetic.render(rng, synthetic.base_sequence(rng, 40)) for _ in range(3)])
+    pairs = np.zeros((0, 2), np.int32)
+    located = {"qmax": ((0,), torch.float32), "seg": ((0, 4), torch.int32), "oti": ((0,), torch.int32)}
+    want = {
+        "crp_align": {"qmax": ((0,), torch.float32), "dmax": ((0,), torch.float32), "oti": ((0,), torch.int32)},
+        "crp_locate": located,
+        "crp_path": dict(located, path_off=((1,), torch.int64), cells=((0, 2), torch.int32)),
+    }
+    got = {"crp_align": bank.crp_align(pairs, qmax=True, dmax=True, want_oti=True),
+           "crp_locate": bank.crp_locate(pairs), "crp_path": bank.crp_path(pairs)}
+    for name, keys in want.items():
+        assert sorted(got[name]) == sorted(keys), name
+        for key, (shape, dtype) in keys.items():
+            t = got[name][key]
+            assert t.is_cuda and tuple(t.shape) == shape and t.dtype == dtype, (name, key, t.shape, t.dtype)
+    assert got["crp_path"]["path_off"].tolist() == [0]
+    assert set(bank.crp_align(pairs)) == {"qmax"}
+
+
 @pytest.mark.parametrize("n", [1, 5, 63, 64, 65, 200])
 def test_ds_finish_matches_numpy(n):
     import torch

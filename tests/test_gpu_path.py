@@ -6,6 +6,7 @@ import pytest
 
 import oracle
 import qmax_path_np as qp
+import qmax_trace_np as qt
 from qmax_trace_np import GAMMAS, SEEDS, SHAPES
 from acoss import _lib, synthetic
 
@@ -50,6 +51,35 @@ def test_path_crp_rejects_a_short_path_cap():
     _lib.path_crp(C, path_cap=9)
     with pytest.raises(_lib.AcossHipError):
         _lib.path_crp(C, path_cap=8)
+
+
+def test_given_matrix_entries_agree():
+    """align_crp, locate_crp and path_crp pack and check a matrix the same way: one score, one
+    segment, all three refuse an element above 1, and an empty matrix scores 0 with no segment and
+    no path."""
+    rng = np.random.Generator(np.random.PCG64(0))
+    C = (rng.random((40, 33)) < 0.3).astype(np.uint8)
+    score, seg = qt.qmax_trace(C)
+    assert score > 0
+    a = float(_lib.align_crp(C, 0).item())
+    ls, lg = _lib.locate_crp(C)
+    ps, pg, cells = _lib.path_crp(C)
+    assert a == float(ls.item()) == float(ps.item()) == score
+    assert lg.cpu().numpy().tolist() == pg.cpu().numpy().tolist() == list(seg)
+    assert cells.cpu().numpy()[0].tolist() == list(seg[:2]) and cells.cpu().numpy()[-1].tolist() == list(seg[2:])
+    bad = C.copy()
+    bad[17, 5] = 2
+    for fn in (_lib.align_crp, _lib.locate_crp, _lib.path_crp):
+        with pytest.raises(_lib.AcossHipError):
+            fn(bad)
+    for shape in ((0, 33), (40, 0)):
+        E = np.zeros(shape, np.uint8)
+        assert float(_lib.align_crp(E, 0).item()) == 0.0
+        ls, lg = _lib.locate_crp(E)
+        ps, pg, cells = _lib.path_crp(E)
+        assert float(ls.item()) == 0.0 and float(ps.item()) == 0.0
+        assert lg.cpu().numpy().tolist() == pg.cpu().numpy().tolist() == [-1, -1, -1, -1]
+        assert tuple(cells.shape) == (0, 2)
 
 
 def _paths(got):
@@ -125,6 +155,22 @@ def test_crp_path_small_dp_batches(covers24, monkeypatch):
     P = _lib.crp_params()
     one = _lib.crp_path(feats, off, lens, int(lens.max()), pairs, P)
     monkeypatch.setenv("ACOSS_BATCH_PAIRS", "7")
+    many = _lib.crp_path(feats, off, lens, int(lens.max()), pairs, P)
+    for key in ("qmax", "seg", "oti", "path_off", "cells"):
+        np.testing.assert_array_equal(many[key].cpu().numpy(), one[key].cpu().numpy(), err_msg=key)
+    assert int(one["path_off"][-1]) > 0
+
+
+def test_crp_path_under_a_plane_budget(covers24, monkeypatch):
+    """A plane budget below the batch's planes splits it into DP batches of equal size. 300 frames
+    stack to L = 291 rows of pitch 296, so a plane is ceil(291 / 16) * 296 * 4 = 22,496 B, 22,528 B
+    aligned to 256; 1,200,000 B hold 53 of them, 276 pairs need ceil(276 / 53) = 6 batches, and six
+    equal ones have ceil(276 / 6) = 46 pairs: neither one batch nor one pair per batch."""
+    tracks, pairs = covers24
+    feats, off, lens = synthetic.pack(tracks)
+    P = _lib.crp_params()
+    one = _lib.crp_path(feats, off, lens, int(lens.max()), pairs, P)
+    monkeypatch.setenv("ACOSS_PATH_BYTES", "1200000")
     many = _lib.crp_path(feats, off, lens, int(lens.max()), pairs, P)
     for key in ("qmax", "seg", "oti", "path_off", "cells"):
         np.testing.assert_array_equal(many[key].cpu().numpy(), one[key].cpu().numpy(), err_msg=key)

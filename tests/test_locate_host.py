@@ -112,3 +112,19 @@ def test_segment_frames_by_hand():
     assert q.tolist() == [[20, 210]] and r.tolist() == [[0, 130]]
     q, r = segment_frames(np.zeros((0, 4), np.int32), 9, 1, 40, [], [])
     assert q.shape == (0, 2) and r.shape == (0, 2)
+
+
+def test_stacked_len_is_the_c_formula():
+    """engine.stacked_len against common.hpp's stacked_len written out (C division truncates; the
+    operands are positive where it is reached), and against the two expressions that crp_pair and
+    crp_path once spelled out inline."""
+    from acoss.engine import stacked_len
+    for tau in range(1, 4):
+        for m in range(1, 11):
+            for n in range(0, 61):
+                inc = m * tau
+                c = 0 if (n <= inc or tau <= 0) else int((n - inc + tau - 1) / tau)
+                pair = max(0, -(-(n - m * tau) // tau)) if n > m * tau else 0
+                path = 0 if n <= m * tau else (n - m * tau + tau - 1) // tau
+                assert stacked_len(n, m, tau) == c == pair == path, (n, m, tau)
+    assert stacked_len(300) == 291  # the defaults are the reference's m = 9, tau = 1
