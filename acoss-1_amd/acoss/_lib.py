@@ -52,6 +52,11 @@ SIGNATURES = {
     "acoss_crp_path": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _i32, _vp, _vp,
                        _vp],
     "acoss_path_crp": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp, _vp, _vp],
+    "acoss_crp_locate_dmax": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _vp],
+    "acoss_locate_crp_dmax": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
+    "acoss_crp_path_dmax": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _i32, _vp,
+                            _vp, _vp],
+    "acoss_path_crp_dmax": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp, _vp, _vp],
     "acoss_sw_constrained": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "acoss_csm": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "acoss_get_oti": [_vp, _vp, _i32, _vp, _vp],
@@ -269,24 +274,47 @@ def align_crp(C, align=0, gamma_open=0.5, gamma_ext=0.5):
     return out
 
 
-def crp_locate(feats, track_off, track_len, max_len, pairs, params):
+def score_key(align):
+    """The result key of the score of the located / traced alignment: align 0 = serra09 ("qmax"), 1 = chen17 ("dmax")."""
+    if align not in (0, 1):
+        raise ValueError("align must be 0 (serra09, Qmax) or 1 (chen17, dmax)")
+    return ("qmax", "dmax")[align]
+
+
+def _aligner(align, name):
+    """(result key of the score, library entry) of the Qmax (align = 0) or dmax (align = 1) form of `name`."""
+    return score_key(align), name + ("_dmax" if align else "")
+
+
+def dmax_path_bound(M, N):
+    """The most cells a dmax (chen17) path of an (M, N) matrix can have: floor(2 (M + N) / 3) - 2 for
+    M, N >= 3 (csrc/crp_internal.hpp dmax_path_bound has the proof). A Qmax path has at most min(M, N)."""
+    return 0 if M < 3 or N < 3 else 2 * (M + N) // 3 - 2
+
+
+def crp_locate(feats, track_off, track_len, max_len, pairs, params, align=0):
     """Batched Qmax with its location (acoss_crp_locate): inputs as crp_align. Returns device tensors
     {"qmax" (P,) f32, "seg" (P, 4) i32 = (i0, j0, i1, j1) in stacked-frame rows / columns, (-1, -1, -1, -1)
-    where Qmax is 0, "oti" (P,) i32}."""
+    where Qmax is 0, "oti" (P,) i32}. align=1: the dmax (chen17) alignment instead
+    (acoss_crp_locate_dmax), the score under "dmax"; its path may begin on an intermediate cell of a
+    (2, 1) or (1, 2) step, so i0 or j0 may be 1 (see crp_path)."""
+    key, entry = _aligner(align, "acoss_crp_locate")
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
-    out = {"qmax": _empty("float32", P), "seg": _empty("int32", P, 4), "oti": _empty("int32", P)}
-    rc = load_library().acoss_crp_locate(*lead, _ptr(out["qmax"]), _ptr(out["seg"]), _ptr(out["oti"]), _stream())
-    _check(rc, "acoss_crp_locate")
+    out = {key: _empty("float32", P), "seg": _empty("int32", P, 4), "oti": _empty("int32", P)}
+    rc = getattr(load_library(), entry)(*lead, _ptr(out[key]), _ptr(out["seg"]), _ptr(out["oti"]), _stream())
+    _check(rc, entry)
     return out
 
 
-def locate_crp(C, gamma_open=0.5, gamma_ext=0.5):
+def locate_crp(C, gamma_open=0.5, gamma_ext=0.5, align=0):
     """Qmax of a binary (M, N) matrix and where it lies (acoss_locate_crp): (score (1,) f32,
-    seg (4,) i32 = (i0, j0, i1, j1)) device tensors; the score is align_crp(C, 0, ...)'s."""
+    seg (4,) i32 = (i0, j0, i1, j1)) device tensors; the score is align_crp(C, 0, ...)'s. align=1:
+    dmax and the chen17 alignment (acoss_locate_crp_dmax), the score align_crp(C, 1, ...)'s."""
+    _, entry = _aligner(align, "acoss_locate_crp")
     C, M, N, go, ge, stream = _matrix_args(C, gamma_open, gamma_ext)
     out, seg = _empty("float32", 1), _empty("int32", 4)
-    rc = load_library().acoss_locate_crp(_ptr(C), M, N, go, ge, _ptr(out), _ptr(seg), stream)
-    _check(rc, "acoss_locate_crp")
+    rc = getattr(load_library(), entry)(_ptr(C), M, N, go, ge, _ptr(out), _ptr(seg), stream)
+    _check(rc, entry)
     return out, seg
 
 
@@ -303,17 +331,24 @@ def _compact_paths(lens, padded):
     return off, padded[keep].reshape(-1, 2)
 
 
-def crp_path(feats, track_off, track_len, max_len, pairs, params):
+def crp_path(feats, track_off, track_len, max_len, pairs, params, align=0):
     """Batched Qmax with its whole alignment path (acoss_crp_path): inputs as crp_align. Returns device
     tensors {"qmax" (P,) f32, "seg" (P, 4) i32 and "oti" (P,) i32 as crp_locate, "path_off" (P + 1,)
     i64, "cells" (total, 2) i32}: the path of pair p is cells[path_off[p]:path_off[p + 1]], (i, j) in
     stacked-frame rows / columns from (i0, j0) to (i1, j1), empty where Qmax is 0. The pairs go to the
-    library in chunks whose padded output stays near PATH_CHUNK_BYTES; each is compacted on the device."""
+    library in chunks whose padded output stays near PATH_CHUNK_BYTES; each is compacted on the device.
+
+    align=1: the dmax (chen17) alignment (acoss_crp_path_dmax), the score under "dmax". Its steps are
+    (1, 1), (2, 1), (1, 2) and, exactly after the intermediate cell of a (2, 1) or (1, 2) step that
+    is a hit, (1, 0) and (0, 1): non-decreasing in i and j, up to dmax_path_bound cells, and i0 or
+    j0 may be 1 (a path may begin on such an intermediate cell, which may lie in row or column 1)."""
     torch = _torch()
     lib = load_library()
+    key, entry = _aligner(align, "acoss_crp_path")
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     pairs = keep[3]
-    cap = max(1, stacked_len(int(max_len), params.m, params.tau))
+    L = stacked_len(int(max_len), params.m, params.tau)
+    cap = max(1, dmax_path_bound(L, L) if align else L)
     q, seg, o = _empty("float32", P), _empty("int32", P, 4), _empty("int32", P)
     lens = _empty("int32", P)
     chunk = max(1, PATH_CHUNK_BYTES // (8 * cap))
@@ -321,28 +356,32 @@ def crp_path(feats, track_off, track_len, max_len, pairs, params):
     for a in range(0, P, chunk):
         n = min(chunk, P - a)
         padded = torch.empty((n, cap, 2), dtype=torch.int32, device="cuda")
-        rc = lib.acoss_crp_path(*lead[:5], _ptr(pairs[a:a + n]), int(n), lead[7], _ptr(q[a:a + n]),
-                                _ptr(seg[a:a + n]), _ptr(o[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded),
-                                _stream())
-        _check(rc, "acoss_crp_path")
+        rc = getattr(lib, entry)(*lead[:5], _ptr(pairs[a:a + n]), int(n), lead[7], _ptr(q[a:a + n]),
+                                 _ptr(seg[a:a + n]), _ptr(o[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded),
+                                 _stream())
+        _check(rc, entry)
         parts.append(_compact_paths(lens[a:a + n], padded)[1])
     off = torch.zeros(P + 1, dtype=torch.int64, device="cuda")
     off[1:] = torch.cumsum(lens.to(torch.int64), 0)
     cells = torch.cat(parts) if parts else torch.empty((0, 2), dtype=torch.int32, device="cuda")
-    return {"qmax": q, "seg": seg, "oti": o, "path_off": off, "cells": cells}
+    return {key: q, "seg": seg, "oti": o, "path_off": off, "cells": cells}
 
 
-def path_crp(C, gamma_open=0.5, gamma_ext=0.5, path_cap=None):
+def path_crp(C, gamma_open=0.5, gamma_ext=0.5, path_cap=None, align=0):
     """Qmax of a binary (M, N) matrix and its alignment path (acoss_path_crp): (score (1,) f32, seg (4,)
     i32, cells (len, 2) i32) device tensors; score and seg are locate_crp's. path_cap: entries of the
-    padded buffer handed to the library, min(M, N) unless given (a smaller one is refused)."""
+    padded buffer handed to the library, min(M, N) unless given (a smaller one is refused). align=1:
+    dmax and the chen17 path (acoss_path_crp_dmax; steps and length as crp_path describes them),
+    path_cap dmax_path_bound(M, N) unless given."""
+    _, entry = _aligner(align, "acoss_path_crp")
     C, M, N, go, ge, stream = _matrix_args(C, gamma_open, gamma_ext)
-    cap = max(1, min(M, N)) if path_cap is None else int(path_cap)
+    bound = dmax_path_bound(M, N) if align else min(M, N)
+    cap = max(1, bound) if path_cap is None else int(path_cap)
     out, seg, n = _empty("float32", 1), _empty("int32", 4), _empty("int32", 1)
     padded = _empty("int32", max(1, cap), 2)
-    rc = load_library().acoss_path_crp(_ptr(C), M, N, go, ge, _ptr(out), _ptr(seg), cap, _ptr(n), _ptr(padded),
-                                       stream)
-    _check(rc, "acoss_path_crp")
+    rc = getattr(load_library(), entry)(_ptr(C), M, N, go, ge, _ptr(out), _ptr(seg), cap, _ptr(n), _ptr(padded),
+                                        stream)
+    _check(rc, entry)
     return out, seg, padded[:int(n.item())]
 
 

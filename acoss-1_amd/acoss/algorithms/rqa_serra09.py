@@ -73,35 +73,51 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
     def _score(self, idxs, dmax=False):
         return {k: v.cpu().numpy() for k, v in self._score_dev(idxs, dmax).items()}
 
-    def localize(self, idxs):
+    _ALIGNMENTS = {"qmax": 0, "dmax": 1}  # serra09 / chen17, the library's align
+
+    def _alignment(self, alignment):
+        if alignment not in self._ALIGNMENTS:
+            raise ValueError("alignment must be 'qmax' (serra09) or 'dmax' (chen17), not %r" % (alignment,))
+        return self._ALIGNMENTS[alignment]
+
+    def localize(self, idxs, alignment="qmax"):
         """Where the Qmax alignment of every (query, reference) pair of idxs lies: a dict of host
         arrays 'qmax' (P,), 'oti' (P,), 'cells' (P, 4) = (i0, j0, i1, j1) in stacked-frame rows and
         columns of the pair's CRP, and 'query_frames' / 'reference_frames' (P, 2): half-open ranges
         in frames of `chroma_type` before downsampling (engine.segment_frames). A pair whose Qmax
         is 0 has cells (-1, -1, -1, -1) and ranges (-1, -1). Not collective: a rank localises the
-        pairs it is given."""
+        pairs it is given.
+        alignment="dmax": the chen17 alignment instead, its score under 'dmax' in place of 'qmax'.
+        That path may begin on the intermediate cell of a (2, 1) or (1, 2) step, so i0 or j0 may be 1
+        (a Qmax path never begins before row and column 2)."""
+        align = self._alignment(alignment)
         self.prepare()
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = self._bank.crp_locate(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti)
+        r = self._bank.crp_locate(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti, align=align)
         cells = r["seg"].cpu().numpy()
         qf, rf = segment_frames(cells, self.m, self.tau, self.downsample_fac, self._n_frames[idxs[:, 0]],
                                 self._n_frames[idxs[:, 1]])
-        return {"qmax": r["qmax"].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": cells,
+        return {alignment: r[alignment].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": cells,
                 "query_frames": qf, "reference_frames": rf}
 
-    def align_path(self, idxs):
+    def align_path(self, idxs, alignment="qmax"):
         """The Qmax alignment of every (query, reference) pair of idxs, cell by cell: a dict of host
         arrays 'qmax' (P,), 'oti' (P,) and 'cells' (P, 4) as localize, 'path_off' (P + 1,) int64,
         'path_cells' (total, 2) int32 and 'path_frames' (total, 2) int64. The path of pair p is
         path_cells[path_off[p]:path_off[p + 1]]: (i, j) in stacked-frame rows and columns of the
         pair's CRP from cells[p, :2] to cells[p, 2:], each step (1, 1), (2, 1) or (1, 2);
         path_frames holds the first frame of `chroma_type` before downsampling of each of them
-        (engine.path_frames). A pair whose Qmax is 0 has an empty path. Not collective."""
+        (engine.path_frames). A pair whose Qmax is 0 has an empty path. Not collective.
+        alignment="dmax": the chen17 alignment instead, its score under 'dmax' in place of 'qmax'.
+        Its five steps are (1, 1), (2, 1), (1, 2) and, exactly after the intermediate cell that a
+        (2, 1) or (1, 2) step passed and that is a hit, (1, 0) and (0, 1): non-decreasing in i and j,
+        possibly longer than the shorter track, and i0 or j0 may be 1."""
+        align = self._alignment(alignment)
         self.prepare()
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = self._bank.crp_path(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti)
+        r = self._bank.crp_path(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti, align=align)
         pc = r["cells"].cpu().numpy()
-        return {"qmax": r["qmax"].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": r["seg"].cpu().numpy(),
+        return {alignment: r[alignment].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": r["seg"].cpu().numpy(),
                 "path_off": r["path_off"].cpu().numpy(), "path_cells": pc,
                 "path_frames": path_frames(pc, self.tau, self.downsample_fac)}
 

@@ -93,7 +93,10 @@ class ChromaBank:
         params = _lib.crp_params(*crp)
         return fn(self.feats, self.off, self.len, self.max_len, pairs, params, **want)
 
-    _LOCATED = (("qmax", 0, "float32"), ("seg", (0, 4), "int32"), ("oti", 0, "int32"))
+    @staticmethod
+    def _located(align):
+        """(key, shape, dtype name) of what crp_locate returns, for an empty pair list."""
+        return ((_lib.score_key(align), 0, "float32"), ("seg", (0, 4), "int32"), ("oti", 0, "int32"))
 
     def crp_align(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, qmax=True,
                   dmax=False, want_oti=False):
@@ -103,14 +106,17 @@ class ChromaBank:
         return self._crp(_lib.crp_align, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext),
                          qmax=qmax, dmax=dmax, oti=want_oti)
 
-    def crp_locate(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5):
+    def crp_locate(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0):
         """Qmax of (query, reference) pairs and where it lies: {"qmax", "seg" (P, 4), "oti"} device
-        tensors (see _lib.crp_locate); the scores are crp_align's."""
-        return self._crp(_lib.crp_locate, self._LOCATED, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext))
+        tensors (see _lib.crp_locate); the scores are crp_align's. align=1: dmax and the chen17
+        alignment, the score under "dmax"."""
+        return self._crp(_lib.crp_locate, self._located(align), pairs, (m, tau, kappa, oti, gamma_open, gamma_ext),
+                         align=align)
 
-    def crp_path(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5):
+    def crp_path(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0):
         """Qmax of (query, reference) pairs with the whole alignment path of each: {"qmax", "seg"
         (P, 4), "oti", "path_off" (P + 1,), "cells" (total, 2)} device tensors (see _lib.crp_path);
-        scores and segments are crp_locate's."""
-        empty = self._LOCATED + (("path_off", 1, "int64"), ("cells", (0, 2), "int32"))
-        return self._crp(_lib.crp_path, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext))
+        scores and segments are crp_locate's. align=1: dmax and the chen17 path, the score under
+        "dmax"; its steps also include (1, 0) and (0, 1) and i0 or j0 may be 1 (_lib.crp_path)."""
+        empty = self._located(align) + (("path_off", 1, "int64"), ("cells", (0, 2), "int32"))
+        return self._crp(_lib.crp_path, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext), align=align)

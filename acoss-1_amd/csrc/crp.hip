@@ -23,8 +23,9 @@
 //  * k_crp_panel: recomputes the distances of a 32-row x 256-column panel and writes the
 //    CRP as one 32-bit word per (32-row strip, column): the layout the DP consumes.
 // The wavefront DP over those words (k_crp_dp*, k_crp_dp_trace for acoss_crp_locate /
-// acoss_locate_crp, k_crp_dp_dir and k_crp_backtrack for acoss_crp_path / acoss_path_crp) is
-// crp_dp.hip; this file reaches it through launch_dp, launch_trace, launch_dir and launch_backtrack.
+// acoss_locate_crp, k_crp_dp_dir and k_crp_backtrack for acoss_crp_path / acoss_path_crp, each also
+// for chen17 under the _dmax entries) is crp_dp.hip; this file reaches it through launch_dp,
+// launch_trace, launch_dir and launch_backtrack.
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -987,10 +988,17 @@ extern "C" int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t
   return matrix_finish(V, s);
 }
 
-extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, const int32_t* track_len,
-                                int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
-                                const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
-                                void* hip_stream) {
+// The four pairs of entries below share one body each; align (launch_dp's: 0 = Qmax, 1 = dmax) picks
+// the lane policy and, for the paths, the backtrack and the length a path can reach.
+namespace {
+
+// the fewest path_out entries per pair an entry accepts for matrices of at most M x N
+int path_bound(int align, int M, int N) { return align == 0 ? (M < N ? M : N) : dmax_path_bound(M, N); }
+
+int crp_locate_any(int align, const float* feats, const int64_t* track_off, const int32_t* track_len,
+                   int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                   const acoss_crp_params* params, float* score_out, int32_t* seg_out, int32_t* oti_out,
+                   void* hip_stream) {
   clear_error();
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   void* tb = nullptr;  // band-boundary records of the tracing DP, tstride per pair
@@ -1011,19 +1019,19 @@ extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, co
       },
       [&](const CrpPlan& C, int64_t base, int nb) {
         prof_begin(PH_DP_TRACE, s);
-        launch_trace(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, tb, tstride,
-                     qmax_out ? qmax_out + base : nullptr, seg_out + 4 * base, s);
+        launch_trace(align, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, tb,
+                     tstride, score_out ? score_out + base : nullptr, seg_out + 4 * base, s);
         ACOSS_LAUNCH_CHECK();
         prof_end(PH_DP_TRACE, s);
         return ACOSS_OK;
       });
 }
 
-extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
-                                float* score_out, int32_t* seg_out, void* hip_stream) {
+int locate_crp_any(int align, const char* entry, const uint8_t* crp, int32_t M, int32_t N, float gamma_open,
+                   float gamma_ext, float* score_out, int32_t* seg_out, void* hip_stream) {
   clear_error();
   if (M < 0 || N < 0 || !score_out || !seg_out) {
-    set_error("bad arguments to acoss_locate_crp");
+    set_error("bad arguments to %s", entry);
     return ACOSS_E_ARG;
   }
   int rc;
@@ -1033,15 +1041,15 @@ extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float 
   MatrixView V;
   const size_t bnd_bytes = kTraceRecBytes * (size_t)trace_bnd_records(M, matrix_pitch(N));
   if ((rc = pack_matrix(SLOT_LOCATE_CRP, crp, M, N, bnd_bytes, 0, s, V))) return rc;
-  launch_trace(1, M, V.maskT, 0, V.ld, V.d_dims, gamma_open, gamma_ext, V.region[0], 0, score_out, seg_out, s);
+  launch_trace(align, 1, M, V.maskT, 0, V.ld, V.d_dims, gamma_open, gamma_ext, V.region[0], 0, score_out, seg_out, s);
   ACOSS_LAUNCH_CHECK();
   return matrix_finish(V, s);
 }
 
-extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, const int32_t* track_len,
-                              int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
-                              const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
-                              int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+int crp_path_any(int align, const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                 int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                 float* score_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
+                 int32_t* path_out, void* hip_stream) {
   clear_error();
   if (path_cap < 0) {
     set_error("negative size");
@@ -1061,9 +1069,15 @@ extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, cons
         }
         const int Lmax = stacked_len(max_len, params->m, params->tau);
         if (int rc = check_cell_bits(Lmax)) return rc;
-        if (path_cap < Lmax) {
+        if (align == 0 && path_cap < Lmax) {
           set_error("path_cap %d below the longest stacked length %d: a path may have that many cells", path_cap,
                     Lmax);
+          return ACOSS_E_ARG;
+        }
+        if (align == 1 && path_cap < path_bound(1, Lmax, Lmax)) {
+          set_error("path_cap %d below %d = floor(4 L / 3) - 2 at the longest stacked length L = %d: a dmax path may "
+                    "have that many cells",
+                    path_cap, path_bound(1, Lmax, Lmax), Lmax);
           return ACOSS_E_ARG;
         }
         return ACOSS_OK;
@@ -1083,31 +1097,37 @@ extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, cons
       },
       [&](const CrpPlan& C, int64_t base, int nb) {
         prof_begin(PH_DP_DIR, s);
-        launch_dir(nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, bnd, bstride,
-                   plane, pstride, endkey, qmax_out ? qmax_out + base : nullptr, s);
+        launch_dir(align, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, bnd,
+                   bstride, plane, pstride, endkey, score_out ? score_out + base : nullptr, s);
         ACOSS_LAUNCH_CHECK();
         prof_end(PH_DP_DIR, s);
         prof_begin(PH_BACKTRACK, s);
-        launch_backtrack(nb, plane, pstride, C.ld, C.dims, endkey, path_cap, seg_out ? seg_out + 4 * base : nullptr,
-                         len_out + base, path_out + 2 * (size_t)path_cap * (size_t)base, s);
+        launch_backtrack(align, nb, plane, pstride, C.mask, C.mask_stride, C.ld, C.dims, endkey, path_cap,
+                         seg_out ? seg_out + 4 * base : nullptr, len_out + base,
+                         path_out + 2 * (size_t)path_cap * (size_t)base, s);
         ACOSS_LAUNCH_CHECK();
         prof_end(PH_BACKTRACK, s);
         return ACOSS_OK;
       });
 }
 
-extern "C" int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
-                              float* score_out, int32_t* seg_out, int32_t path_cap, int32_t* len_out,
-                              int32_t* path_out, void* hip_stream) {
+int path_crp_any(int align, const char* entry, const uint8_t* crp, int32_t M, int32_t N, float gamma_open,
+                 float gamma_ext, float* score_out, int32_t* seg_out, int32_t path_cap, int32_t* len_out,
+                 int32_t* path_out, void* hip_stream) {
   clear_error();
   if (M < 0 || N < 0 || path_cap < 0 || !score_out || !len_out || !path_out) {
-    set_error("bad arguments to acoss_path_crp");
+    set_error("bad arguments to %s", entry);
     return ACOSS_E_ARG;
   }
   int rc;
   if ((rc = check_cell_bits(M, N))) return rc;
-  if (path_cap < (M < N ? M : N)) {
-    set_error("path_cap %d below min(M, N) = %d: a path may have that many cells", path_cap, M < N ? M : N);
+  if (align == 0 && path_cap < path_bound(0, M, N)) {
+    set_error("path_cap %d below min(M, N) = %d: a path may have that many cells", path_cap, path_bound(0, M, N));
+    return ACOSS_E_ARG;
+  }
+  if (align == 1 && path_cap < path_bound(1, M, N)) {
+    set_error("path_cap %d below floor(2 (M + N) / 3) - 2 = %d: a dmax path may have that many cells", path_cap,
+              path_bound(1, M, N));
     return ACOSS_E_ARG;
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -1118,11 +1138,68 @@ extern "C" int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float ga
                         (size_t)dir_plane_bytes(M, ld), s, V)))
     return rc;
   uint8_t* plane = reinterpret_cast<uint8_t*>(V.region[1]);
-  launch_dir(1, M, V.maskT, 0, ld, V.d_dims, gamma_open, gamma_ext, reinterpret_cast<float4*>(V.region[0]), 0, plane,
-             0, V.d_end, score_out, s);
+  launch_dir(align, 1, M, V.maskT, 0, ld, V.d_dims, gamma_open, gamma_ext, reinterpret_cast<float4*>(V.region[0]), 0,
+             plane, 0, V.d_end, score_out, s);
   ACOSS_LAUNCH_CHECK();
-  launch_backtrack(1, plane, 0, ld, V.d_dims, V.d_end, path_cap, seg_out, len_out, path_out, s);
+  launch_backtrack(align, 1, plane, 0, V.maskT, 0, ld, V.d_dims, V.d_end, path_cap, seg_out, len_out, path_out, s);
   ACOSS_LAUNCH_CHECK();
   return matrix_finish(V, s);
 }
 
+}  // namespace
+
+extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                                void* hip_stream) {
+  return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, qmax_out, seg_out,
+                        oti_out, hip_stream);
+}
+
+extern "C" int acoss_crp_locate_dmax(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                     int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                     const acoss_crp_params* params, float* dmax_out, int32_t* seg_out,
+                                     int32_t* oti_out, void* hip_stream) {
+  return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, dmax_out, seg_out,
+                        oti_out, hip_stream);
+}
+
+extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                                float* score_out, int32_t* seg_out, void* hip_stream) {
+  return locate_crp_any(0, "acoss_locate_crp", crp, M, N, gamma_open, gamma_ext, score_out, seg_out, hip_stream);
+}
+
+extern "C" int acoss_locate_crp_dmax(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                                     float* score_out, int32_t* seg_out, void* hip_stream) {
+  return locate_crp_any(1, "acoss_locate_crp_dmax", crp, M, N, gamma_open, gamma_ext, score_out, seg_out, hip_stream);
+}
+
+extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                              int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                              const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                              int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, qmax_out, seg_out,
+                      oti_out, path_cap, len_out, path_out, hip_stream);
+}
+
+extern "C" int acoss_crp_path_dmax(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                   int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                   const acoss_crp_params* params, float* dmax_out, int32_t* seg_out, int32_t* oti_out,
+                                   int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, dmax_out, seg_out,
+                      oti_out, path_cap, len_out, path_out, hip_stream);
+}
+
+extern "C" int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                              float* score_out, int32_t* seg_out, int32_t path_cap, int32_t* len_out,
+                              int32_t* path_out, void* hip_stream) {
+  return path_crp_any(0, "acoss_path_crp", crp, M, N, gamma_open, gamma_ext, score_out, seg_out, path_cap, len_out,
+                      path_out, hip_stream);
+}
+
+extern "C" int acoss_path_crp_dmax(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                                   float* score_out, int32_t* seg_out, int32_t path_cap, int32_t* len_out,
+                                   int32_t* path_out, void* hip_stream) {
+  return path_crp_any(1, "acoss_path_crp_dmax", crp, M, N, gamma_open, gamma_ext, score_out, seg_out, path_cap,
+                      len_out, path_out, hip_stream);
+}

@@ -11,8 +11,8 @@
 //  * a lane policy: what a lane keeps per column and the recurrence on it (step).
 //      DpLane    f32 scores, any gamma and both alignments; FAST: serra09 at gamma = K/2
 //      DpLanePk  chen17 at gamma = K/2 in packed 16-bit integers, two rows per instruction
-//      DpLaneT   serra09 with the cell where each path began carried beside every score
-//      DpLaneD   serra09 scores that leave a 2-bit predecessor code per cell in a plane
+//      DpLaneT   either alignment with the cell where each path began carried beside every score
+//      DpLaneD   either alignment's scores that leave a 2-bit predecessor code per cell in a plane
 //  * an edge policy: what is above the chain's first lane and below its last one.
 //      Band       the band above / below, through HBM records
 //      GroupEdge  nothing above, nothing kept: several short pairs per wave, one band each
@@ -23,9 +23,10 @@
 //  k_crp_dp_fast<R>          the same with the FAST step
 //  k_crp_dp_grp              FAST at 32 rows per lane, 64 / ceil(L / 32) pairs per wave
 //  k_crp_dp_pk<1>            DpLanePk in bands
-//  k_crp_dp_trace<EQG, R>    DpLaneT in bands, for acoss_crp_locate / acoss_locate_crp
-//  k_crp_dp_dir<EQG, R>      DpLaneD in bands, and k_crp_backtrack, the walk back over its plane,
-//                            for acoss_crp_path / acoss_path_crp
+//  k_crp_dp_trace<ALIGN, EQG, R>  DpLaneT in bands, for acoss_crp_locate / acoss_locate_crp (ALIGN 0)
+//                            and acoss_crp_locate_dmax / acoss_locate_crp_dmax (ALIGN 1)
+//  k_crp_dp_dir<ALIGN, EQG, R>    DpLaneD in bands, and k_crp_backtrack / k_crp_backtrack_dmax, the walk
+//                            back over its plane, for acoss_crp_path / acoss_path_crp and their _dmax twins
 // launch_dp, launch_trace and launch_dir choose among them.
 #include <cstdlib>
 #include <type_traits>
@@ -492,6 +493,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 //    with row_lo < M' <= row_hi and leaves the others to the launch of the other R.
 //  * the values handed to the next lane, and across a band boundary through HBM, are the last two
 //    rows' scores, CRP bits and origins (TraceRec).
+//  * ALIGN = 1 is chen17 (dmax; the definition: include/acoss_hip.h, acoss_crp_locate_dmax): b and
+//    c carry the bonus bits C[r-1][c] and C[r][c-1], taken from the extended words as DpLane<1>
+//    takes them (row 0 of a lane reads the last row of the lane or band above), and where such a
+//    predecessor scores 0 its origin is the intermediate cell's key, key - 65536 for b and key - 1
+//    for c: if that choice wins with a positive value, the intermediate is a hit and the path
+//    begins there. The bonus is added before the common subtraction, so the halves select holds.
+//    Two more selects per cell: 106 registers at R = 8 (4 waves per SIMD), 168 at R = 16 (3).
 // Every lane runs every step and selects; the only branches around a shuffle are wave-uniform.
 // --------------------------------------------------------------------------------------
 struct DpAboveT {   // what lane l-1 (or the band above) hands down for one column
@@ -506,7 +514,7 @@ struct TraceRec {  // one column of a band boundary, 32 B
 };
 static_assert(sizeof(TraceRec) == kTraceRecBytes, "callers size the boundary buffer by kTraceRecBytes");
 
-template <bool EQG, int R>
+template <int ALIGN, bool EQG, int R>
 struct DpLaneT {
   static_assert(R <= 16, "the extended CRP words are 32-bit");
   static constexpr int kRows = R;
@@ -553,11 +561,20 @@ struct DpLaneT {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const float Qa = r >= 1 ? c1.q[r - 1] : h1.q31;                        // Q[r-1][c-1]
-      const float Qb = r >= 2 ? c1.q[r - 2] : (r == 1 ? h1.q31 : h1.q30);    // Q[r-2][c-1]
-      const float Qc = r >= 1 ? c2.q[r - 1] : h2.q31;                        // Q[r-1][c-2]
+      float Qb = r >= 2 ? c1.q[r - 2] : (r == 1 ? h1.q31 : h1.q30);          // Q[r-2][c-1]
+      float Qc = r >= 1 ? c2.q[r - 1] : h2.q31;                              // Q[r-1][c-2]
       const uint32_t Oa = r >= 1 ? c1.o[r - 1] : h1.o31;
-      const uint32_t Ob = r >= 2 ? c1.o[r - 2] : (r == 1 ? h1.o31 : h1.o30);
-      const uint32_t Oc = r >= 1 ? c2.o[r - 1] : h2.o31;
+      uint32_t Ob = r >= 2 ? c1.o[r - 2] : (r == 1 ? h1.o31 : h1.o30);
+      uint32_t Oc = r >= 1 ? c2.o[r - 1] : h2.o31;
+      if constexpr (ALIGN == 1) {
+        // chen17: a path that comes through b or c from a cell that scores 0 begins on the
+        // intermediate cell the bonus paid for, (i-1, j) or (i, j-1); then the bonus itself
+        const uint32_t xkey = kc + ((uint32_t)r << 16);
+        Ob = Qb > 0.0f ? Ob : xkey - 65536u;
+        Oc = Qc > 0.0f ? Oc : xkey - 1u;
+        Qb = Qb + (float)((e0 >> (r + 1)) & 1u);  // + C[r-1][c]
+        Qc = Qc + (float)((e1 >> (r + 2)) & 1u);  // + C[r][c-1]
+      }
       const bool hit = (e0 >> (r + 2)) & 1u;
       float pa = Qa, pb = Qb, pc = Qc;
       if (!EQG) {
@@ -616,13 +633,16 @@ struct DpLaneT {
 // bnd: ceil(L / (64 R)) * ld TraceRec per pair (bnd_stride records between pairs); only read and
 // written by CRPs of more than one band. qmax_out may be NULL; seg_out: int32[4] (i0, j0, i1, j1) per pair.
 // Waves per SIMD: R = 8 needs 96 registers, exactly the step of 5 waves, and without the floor the
-// unequal-gamma body lands at 100 (4 waves); R = 16 runs at 2 waves or better.
-template <bool EQG, int R>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R == 8 ? 5 : 2))) void k_crp_dp_trace(
+// unequal-gamma body lands at 100 (4 waves); R = 16 runs at 2 waves or better. chen17 at R = 8 needs
+// 106 (126 with unequal gammas): 4 waves.
+constexpr int trace_waves(int align, int R) { return R == 8 ? (align == 0 ? 5 : 4) : 2; }
+
+template <int ALIGN, bool EQG, int R>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(trace_waves(ALIGN, R)))) void k_crp_dp_trace(
     const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld, const int2* __restrict__ dims, int row_lo,
     int row_hi, float go, float ge, TraceRec* __restrict__ bnd, int64_t bnd_stride, float* __restrict__ qmax_out,
     int32_t* __restrict__ seg_out) {
-  using Lane = DpLaneT<EQG, R>;
+  using Lane = DpLaneT<ALIGN, EQG, R>;
   const int p = blockIdx.x;
   const int lane = threadIdx.x;
   const int2 dm = dims[p];
@@ -688,6 +708,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R == 8 ? 5 :
 //    every word a walk can reach is written and the plane is never zeroed.
 //  * R and the bands are the tracing DP's: R = 8 up to 512 rows, 16 above, by the same two
 //    launches; the wave reduces (Qmax, end key) by its rule and leaves the key in endkey[p].
+//  * ALIGN = 1 is chen17: the same codes over the values with their bonus; what else the walk
+//    back needs (is the intermediate cell a hit, does the predecessor score above 0) it reads off
+//    the CRP words and the plane itself, see k_crp_backtrack_dmax.
 // The store sits after the step's shuffles, under the lane's own predicate; every lane runs every
 // step.
 // --------------------------------------------------------------------------------------
@@ -702,7 +725,7 @@ struct DirWord<8> {
   using type = uint16_t;
 };
 
-template <bool EQG, int R>
+template <int ALIGN, bool EQG, int R>
 struct DpLaneD {
   static_assert(R == 8 || R == 16, "2 R code bits are one 16- or 32-bit word");
   static constexpr int kRows = R;
@@ -744,8 +767,12 @@ struct DpLaneD {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const float Qa = r >= 1 ? q1[r - 1] : h1.q31;                        // Q[r-1][c-1]
-      const float Qb = r >= 2 ? q1[r - 2] : (r == 1 ? h1.q31 : h1.q30);    // Q[r-2][c-1]
-      const float Qc = r >= 1 ? q2[r - 1] : h2.q31;                        // Q[r-1][c-2]
+      float Qb = r >= 2 ? q1[r - 2] : (r == 1 ? h1.q31 : h1.q30);          // Q[r-2][c-1]
+      float Qc = r >= 1 ? q2[r - 1] : h2.q31;                              // Q[r-1][c-2]
+      if constexpr (ALIGN == 1) {
+        Qb = Qb + (float)((e0 >> (r + 1)) & 1u);  // + C[r-1][c]
+        Qc = Qc + (float)((e1 >> (r + 2)) & 1u);  // + C[r][c-1]
+      }
       const bool hit = (e0 >> (r + 2)) & 1u;
       float pa = Qa, pb = Qb, pc = Qc;
       if (!EQG) {
@@ -800,13 +827,13 @@ struct DpLaneD {
 
 // bnd: ceil(L / (64 R)) * ld float4 per pair, as the tracing DP's records are counted; plane:
 // pstride bytes between pairs. qmax_out may be NULL.
-template <bool EQG, int R>
+template <int ALIGN, bool EQG, int R>
 __global__ __launch_bounds__(64) void k_crp_dp_dir(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
                                                    const int2* __restrict__ dims, int row_lo, int row_hi, float go,
                                                    float ge, float4* __restrict__ bnd, int64_t bnd_stride,
                                                    uint8_t* __restrict__ plane, int64_t plane_stride,
                                                    uint32_t* __restrict__ endkey, float* __restrict__ qmax_out) {
-  using Lane = DpLaneD<EQG, R>;
+  using Lane = DpLaneD<ALIGN, EQG, R>;
   using Word = typename Lane::Word;
   const int p = blockIdx.x;
   const int lane = threadIdx.x;
@@ -860,6 +887,16 @@ __global__ __launch_bounds__(64) void k_crp_dp_dir(const uint32_t* __restrict__ 
 // first; then the whole wave turns them round in place and fills the rest of the pair's path_cap
 // entries with -1. seg (unless NULL): the first and last cell, (-1, -1, -1, -1) for no path.
 // --------------------------------------------------------------------------------------
+// the n cells a backtrack left in out[], last to first, turned round by the whole wave, and -1 after them
+__device__ __forceinline__ void path_turn_and_pad(int2* out, int n, int path_cap, int lane) {
+  for (int t = lane; t < n / 2; t += 64) {
+    const int2 a = out[t], b = out[n - 1 - t];
+    out[t] = b;
+    out[n - 1 - t] = a;
+  }
+  for (int t = n + lane; t < path_cap; t += 64) out[t] = make_int2(-1, -1);
+}
+
 __global__ __launch_bounds__(64) void k_crp_backtrack(const uint8_t* __restrict__ plane, int64_t plane_stride, int ld,
                                                       const int2* __restrict__ dims,
                                                       const uint32_t* __restrict__ endkey, int path_cap,
@@ -909,13 +946,87 @@ __global__ __launch_bounds__(64) void k_crp_backtrack(const uint8_t* __restrict_
   }
   __threadfence_block();
   __syncthreads();
-  const int n = s_n;
-  for (int t = lane; t < n / 2; t += 64) {
-    const int2 a = out[t], b = out[n - 1 - t];
-    out[t] = b;
-    out[n - 1 - t] = a;
+  path_turn_and_pad(out, s_n, path_cap, lane);
+}
+
+// --------------------------------------------------------------------------------------
+// k_crp_backtrack_dmax: the walk back over a chen17 plane (k_crp_dp_dir<1, ., .>). The code of a
+// cell X names its predecessor P as before, but a b or c step also passed an intermediate cell I,
+// (i-1, j) or (i, j-1), and P may score 0, where the path stops without it. Both are read off the
+// pair's CRP words (strip-major, bit i & 31 of word (i >> 5) ld + j) and the plane:
+//  * I is on the path where C[I] is set: it is the hit the bonus paid for;
+//  * D[P] > 0 exactly where P lies in rows and columns >= 2 and is a hit (D >= 1) or a miss with a
+//    code (a miss without one scores 0); the walk goes on at P then, and otherwise ends on I.
+// Every cell the loop reads lies in [1, M') x [1, N'): X and a P it moves to in [2, M') x [2, N'),
+// I one row or one column before X. It emits at most two cells per turn and tests the count,
+// min(dmax_path_bound(M', N'), path_cap), before each, so whatever the plane holds it ends and
+// writes inside the pair's path_cap entries. The code of P, C[P] and C[I] are three independent
+// loads behind the code of X: one load of latency per step, as in k_crp_backtrack.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_crp_backtrack_dmax(const uint8_t* __restrict__ plane, int64_t plane_stride,
+                                                           const uint32_t* __restrict__ maskT, int64_t mask_stride,
+                                                           int ld, const int2* __restrict__ dims,
+                                                           const uint32_t* __restrict__ endkey, int path_cap,
+                                                           int32_t* __restrict__ seg_out,
+                                                           int32_t* __restrict__ len_out, int32_t* path_out) {
+  __shared__ int s_n;
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  int2* const out = reinterpret_cast<int2*>(path_out) + (size_t)p * path_cap;
+  if (lane == 0) {
+    const int2 dm = dims[p];
+    const int Mp = dm.x, Np = dm.y;
+    const uint32_t key = endkey[p];
+    int i = (int)(key >> 16), j = (int)(key & 0xffffu);
+    int n = 0, i0 = -1, j0 = -1, i1 = -1, j1 = -1;
+    if (key != kNoEnd && i >= 2 && i < Mp && j >= 2 && j < Np) {
+      const uint8_t* const pl = plane + (size_t)p * plane_stride;
+      const uint32_t* const mk = maskT + (size_t)p * mask_stride;
+      const bool r8 = Mp <= kTraceShortRows;
+      const int lim = min(dmax_path_bound(Mp, Np), path_cap);
+      auto code_at = [&](int a, int b) -> uint32_t {
+        if (r8) return ((uint32_t) reinterpret_cast<const uint16_t*>(pl)[(size_t)(a >> 3) * ld + b] >> (2 * (a & 7))) & 3u;
+        return (reinterpret_cast<const uint32_t*>(pl)[(size_t)(a >> 4) * ld + b] >> (2 * (a & 15))) & 3u;
+      };
+      auto crp_at = [&](int a, int b) -> uint32_t { return (mk[(size_t)(a >> 5) * ld + b] >> (a & 31)) & 1u; };
+      i1 = i;
+      j1 = j;
+      uint32_t code = code_at(i, j);
+      while (n < lim) {
+        out[n++] = make_int2(i, j);
+        i0 = i;
+        j0 = j;
+        if (code == 0u) break;
+        const int pi = i - (code == 2u ? 2 : 1), pj = j - (code == 3u ? 2 : 1);
+        const int ii = code == 2u ? i - 1 : i, ij = code == 3u ? j - 1 : j;  // I (X itself for code 1)
+        const bool p_in = pi >= 2 && pj >= 2;
+        const uint32_t pcode = p_in ? code_at(pi, pj) : 0u;
+        const uint32_t phit = p_in ? crp_at(pi, pj) : 0u;
+        if (code != 1u && crp_at(ii, ij)) {
+          if (n >= lim) break;
+          out[n++] = make_int2(ii, ij);
+          i0 = ii;
+          j0 = ij;
+        }
+        if (!(phit | pcode)) break;  // D[P] == 0: the path began on I
+        i = pi;
+        j = pj;
+        code = pcode;
+      }
+    }
+    if (seg_out) {
+      int32_t* sg = seg_out + 4 * (size_t)p;
+      sg[0] = i0;
+      sg[1] = j0;
+      sg[2] = i1;
+      sg[3] = j1;
+    }
+    len_out[p] = n;
+    s_n = n;
   }
-  for (int t = n + lane; t < path_cap; t += 64) out[t] = make_int2(-1, -1);
+  __threadfence_block();
+  __syncthreads();
+  path_turn_and_pad(out, s_n, path_cap, lane);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1006,12 +1117,18 @@ int64_t trace_bnd_records(int L, int ld) {  // per pair: ceil(L / (64 R)) * ld
   return L <= kTraceShortRows ? (int64_t)ld : (int64_t)((L + 64 * 16 - 1) / (64 * 16)) * ld;
 }
 
-void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
-                  void* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s) {
+void launch_trace(int align, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
+                  float ge, void* bnd, int64_t bstride, float* score, int32_t* seg, hipStream_t s) {
   launch_by_rows(L, go, ge, [&](auto r, bool halves, int row_lo, int row_hi) {
     constexpr int R = decltype(r)::value;
-    hipLaunchKernelGGL((halves ? k_crp_dp_trace<true, R> : k_crp_dp_trace<false, R>), dim3(nb), dim3(64), 0, s, maskT,
-                       mstride, ld, dims, row_lo, row_hi, go, ge, static_cast<TraceRec*>(bnd), bstride, qmax, seg);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, row_lo, row_hi, go, ge,
+                         static_cast<TraceRec*>(bnd), bstride, score, seg);
+    };
+    if (align == 0)
+      launch(halves ? k_crp_dp_trace<0, true, R> : k_crp_dp_trace<0, false, R>);
+    else
+      launch(halves ? k_crp_dp_trace<1, true, R> : k_crp_dp_trace<1, false, R>);
   });
 }
 
@@ -1019,20 +1136,31 @@ void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld,
 // CRP of at most 512 rows never take more
 int64_t dir_plane_bytes(int L, int ld) { return (int64_t)((L + 15) / 16) * ld * 4; }
 
-void launch_dir(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
-                float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey, float* qmax,
+void launch_dir(int align, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
+                float ge, float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey, float* score,
                 hipStream_t s) {
   launch_by_rows(L, go, ge, [&](auto r, bool halves, int row_lo, int row_hi) {
     constexpr int R = decltype(r)::value;
-    hipLaunchKernelGGL((halves ? k_crp_dp_dir<true, R> : k_crp_dp_dir<false, R>), dim3(nb), dim3(64), 0, s, maskT,
-                       mstride, ld, dims, row_lo, row_hi, go, ge, bnd, bstride, plane, pstride, endkey, qmax);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nb), dim3(64), 0, s, maskT, mstride, ld, dims, row_lo, row_hi, go, ge, bnd,
+                         bstride, plane, pstride, endkey, score);
+    };
+    if (align == 0)
+      launch(halves ? k_crp_dp_dir<0, true, R> : k_crp_dp_dir<0, false, R>);
+    else
+      launch(halves ? k_crp_dp_dir<1, true, R> : k_crp_dp_dir<1, false, R>);
   });
 }
 
-void launch_backtrack(int nb, const uint8_t* plane, int64_t pstride, int ld, const int2* dims, const uint32_t* endkey,
-                      int path_cap, int32_t* seg, int32_t* len, int32_t* path, hipStream_t s) {
-  hipLaunchKernelGGL(k_crp_backtrack, dim3(nb), dim3(64), 0, s, plane, pstride, ld, dims, endkey, path_cap, seg, len,
-                     path);
+void launch_backtrack(int align, int nb, const uint8_t* plane, int64_t pstride, const uint32_t* maskT, int64_t mstride,
+                      int ld, const int2* dims, const uint32_t* endkey, int path_cap, int32_t* seg, int32_t* len,
+                      int32_t* path, hipStream_t s) {
+  if (align == 0)
+    hipLaunchKernelGGL(k_crp_backtrack, dim3(nb), dim3(64), 0, s, plane, pstride, ld, dims, endkey, path_cap, seg, len,
+                       path);
+  else
+    hipLaunchKernelGGL(k_crp_backtrack_dmax, dim3(nb), dim3(64), 0, s, plane, pstride, maskT, mstride, ld, dims, endkey,
+                       path_cap, seg, len, path);
 }
 
 }  // namespace acoss

@@ -41,25 +41,44 @@ int launch_crp_split(const CrpBatch& B, int nb, int L, float kappa, void* kplane
 // records per pair (bstride between pairs); out[p] = the score.
 void launch_dp(int align, bool eqg, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims,
                float go, float ge, float4* bnd, int64_t bstride, float* out, hipStream_t s);
-// launch_trace: Qmax (qmax may be NULL) and seg[p] = (i0, j0, i1, j1), where its alignment starts
-// and ends, for L <= kTraceMaxLen; bnd: trace_bnd_records(L, ld) records of kTraceRecBytes per pair.
+// launch_trace: the score (may be NULL) and seg[p] = (i0, j0, i1, j1), where its alignment starts and
+// ends, for L <= kTraceMaxLen; align as launch_dp's (the definitions: include/acoss_hip.h,
+// acoss_crp_locate and acoss_crp_locate_dmax); bnd: trace_bnd_records(L, ld) records of
+// kTraceRecBytes per pair.
 constexpr int kTraceMaxLen = 65535;  // 16 bits per coordinate of a packed cell
 constexpr size_t kTraceRecBytes = 32;
 int64_t trace_bnd_records(int L, int ld);
-void launch_trace(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
-                  void* bnd, int64_t bstride, float* qmax, int32_t* seg, hipStream_t s);
-// The Qmax alignment path, cell by cell, for L <= kTraceMaxLen. launch_dir: the direction DP; per
-// pair it fills a plane of 2-bit predecessor codes (dir_plane_bytes(L, ld) bytes, pstride bytes
-// between pairs) and endkey[p] = (i1 << 16) | j1 (kNoEnd where Qmax is 0); qmax may be NULL; bnd:
+void launch_trace(int align, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
+                  float ge, void* bnd, int64_t bstride, float* score, int32_t* seg, hipStream_t s);
+// The alignment path, cell by cell, for L <= kTraceMaxLen. launch_dir: the direction DP; per pair
+// it fills a plane of 2-bit predecessor codes (dir_plane_bytes(L, ld) bytes, pstride bytes between
+// pairs) and endkey[p] = (i1 << 16) | j1 (kNoEnd where the score is 0); score may be NULL; bnd:
 // trace_bnd_records(L, ld) float4 records per pair. launch_backtrack: walks each pair's plane from
-// its end cell and writes len[p] cells (i, j), first to last, to path + 2 path_cap p (the rest -1)
-// and, unless seg is NULL, launch_trace's seg[p].
+// its end cell (align 1 also reads the pair's CRP words) and writes len[p] cells (i, j), first to
+// last, to path + 2 path_cap p (the rest -1) and, unless seg is NULL, launch_trace's seg[p].
 constexpr uint32_t kNoEnd = 0xffffffffu;
 int64_t dir_plane_bytes(int L, int ld);
-void launch_dir(int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go, float ge,
-                float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey, float* qmax,
+void launch_dir(int align, int nb, int L, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, float go,
+                float ge, float4* bnd, int64_t bstride, uint8_t* plane, int64_t pstride, uint32_t* endkey, float* score,
                 hipStream_t s);
-void launch_backtrack(int nb, const uint8_t* plane, int64_t pstride, int ld, const int2* dims, const uint32_t* endkey,
-                      int path_cap, int32_t* seg, int32_t* len, int32_t* path, hipStream_t s);
+void launch_backtrack(int align, int nb, const uint8_t* plane, int64_t pstride, const uint32_t* maskT, int64_t mstride,
+                      int ld, const int2* dims, const uint32_t* endkey, int path_cap, int32_t* seg, int32_t* len,
+                      int32_t* path, hipStream_t s);
+
+// The most cells a dmax (chen17) path of an M x N matrix can have: floor(2 (M + N) / 3) - 2 for
+// M, N >= 3, none below. Proof. Call the cells with a DP value the chain X_0 .. X_n (X_n the end
+// cell); all lie in rows and columns >= 2, so i + j is at least 4 at X_0 and at most M + N - 2 at
+// X_n. From X_(t-1) to X_t the sum i + j grows by 2 on an a step, which adds one cell (X_t), and by
+// 3 on a b or c step, which adds at most two (X_t and its intermediate). With s steps of the first
+// and t of the second kind, 2 s + 3 t <= M + N - 6 =: F, and s + 2 t is largest at t = floor(F / 3),
+// s = 1 if F mod 3 == 2 else 0, i.e. floor(2 F / 3) (a unit of i + j buys 1/2 cell by a, 2/3 by b or
+// c). Before X_1 come X_0 and at most one more cell, the intermediate the path began on. Together
+// 2 + floor(2 (M + N - 6) / 3) = floor(2 (M + N) / 3) - 2. The bound is met: 2 cells at 3 x 3, and
+// the b / c staircases of tests/dmax_path_np.py come within two cells of it on square matrices. It
+// grows with M and with N, so the bound at the longest stacked length serves every pair of a batch.
+// The same number: acoss/_lib.py dmax_path_bound, tests/dmax_path_np.py path_bound.
+__host__ __device__ constexpr int dmax_path_bound(int M, int N) {
+  return (M < 3 || N < 3) ? 0 : 2 * (M + N) / 3 - 2;
+}
 
 }  // namespace acoss

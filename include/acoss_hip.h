@@ -94,7 +94,8 @@ int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t align, flo
  * (i0, j0), by origin propagation inside the DP (crp_dp.hip k_crp_dp_trace); no M' x N' score matrix
  * is written. A path extends through the predecessors (i-1, j-1), (i-2, j-1), (i-1, j-2) in that
  * order, the first one attaining the maximum wins; a hit whose predecessors are all 0 starts one.
- * serra09 only. seg_out: int32[4 n_pairs] = (i0, j0, i1, j1) in stacked-frame rows (query) and
+ * serra09; acoss_crp_locate_dmax below is its chen17 twin.
+ * seg_out: int32[4 n_pairs] = (i0, j0, i1, j1) in stacked-frame rows (query) and
  * columns (reference); qmax_out, oti_out may be NULL; seg_out must not be. A pair whose Qmax is 0
  * gets (-1, -1, -1, -1). The CRP is the one acoss_crp_align computes (same kernels, same
  * workspace), qmax_out is its qmax_out bit for bit. A stacked length above 65,535 returns
@@ -115,7 +116,8 @@ int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open,
  * where needed), and k_crp_backtrack walks it from the end cell. The path of a pair is the chain
  * of chosen predecessors (same order and tie rule as acoss_crp_locate) from (i1, j1) back to a
  * cell without one, reported from (i0, j0) to (i1, j1): strictly increasing in i and j, steps
- * (1, 1), (2, 1), (1, 2), at most min(M', N') cells, empty where Qmax is 0. serra09 only.
+ * (1, 1), (2, 1), (1, 2), at most min(M', N') cells, empty where Qmax is 0. serra09; chen17 has
+ * acoss_crp_path_dmax below.
  * path_out: int32[n_pairs][path_cap][2] of (i, j) in stacked-frame rows and columns; the first
  * len_out[p] entries of pair p are its path, the others hold -1. path_cap must be at least the
  * stacked length of max_len (ACOSS_E_ARG otherwise; no pair's path is longer). qmax_out, seg_out,
@@ -132,6 +134,55 @@ int acoss_crp_path(const float* feats, const int64_t* track_off, const int32_t* 
  * ACOSS_E_SHAPE. A matrix with fewer than 3 rows or columns has score 0 and an empty path. */
 int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext, float* score_out,
                    int32_t* seg_out, int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream);
+
+/* Where the dmax (chen17) alignment lies and which cells it passes: the four entries above for the
+ * other aligner, argument for argument, with dmax_out in place of qmax_out. dmax_out is
+ * acoss_crp_align's dmax_out (score_out acoss_align_crp's at align = 1) bit for bit, whichever of
+ * its score kernels that call runs. Same kernels around the same walk (crp_dp.hip
+ * k_crp_dp_trace<1, ., .>, k_crp_dp_dir<1, ., .>, k_crp_backtrack_dmax), same workspace, same
+ * conventions (seg_out = (i0, j0, i1, j1), path_out padded with -1) and the same refusals.
+ *
+ * The definition. C is the binary M x N matrix, D the chen17 score matrix of
+ * oracle/crp_oracle.cpp or_align(which = 1), all arithmetic float32; cells with i < 2 or j < 2 hold
+ * 0; g(c) = gamma_open if c is set, else gamma_ext. The predecessors of X = (i, j), i, j >= 2, in
+ * this fixed order, each with the cell it steps over and its raw value:
+ *     a: P = (i-1, j-1), no intermediate,  D[P]
+ *     b: P = (i-2, j-1), I = (i-1, j),     D[P] + C[I]
+ *     c: P = (i-1, j-2), I = (i, j-1),     D[P] + C[I]
+ *   score: on a hit D[X] = max(raw) + 1; on a miss D[X] = max(0, max_k (raw_k - g(C[P_k]))).
+ *   chosen predecessor: the FIRST of a, b, c attaining the maximum, taken over the raw values on a
+ *     hit and over the penalised values on a miss (a strictly greater value replaces, an equal one
+ *     does not). A hit whose maximum is 0 has none (a path starts at X), nor has a cell with
+ *     D[X] == 0.
+ *   path: the chain from the end cell backwards. At X with chosen predecessor k: if I exists and
+ *     C[I] is set, I is on the path (the hit the bonus paid for); if D[P] > 0 the chain goes on at
+ *     P; otherwise the path begins at I, the only other way a path starts, and I is then a hit.
+ *     A P in row or column 0 or 1 has D = 0 whatever C holds there; an I may lie in row 1 or
+ *     column 1, it is a real cell of the matrix and is reported, so i0 or j0 may be 1.
+ *   end cell: the first cell in row-major order holding dmax; segment: (first path cell, end
+ *     cell), (-1, -1, -1, -1) where dmax is 0.
+ *   order and steps: from origin to end; steps (1, 1), (2, 1), (1, 2) and, exactly after an
+ *     intermediate cell, (1, 0) and (0, 1): non-decreasing in i and j, not strictly increasing.
+ *   length: at most floor(2 (M + N) / 3) - 2 cells for M, N >= 3 (a diagonal step adds one cell
+ *     for two of rows plus columns, a b or c step two for three, a start on an intermediate one
+ *     more; crp_internal.hpp dmax_path_bound has the proof), so more than min(M, N) is possible.
+ *   Origins are defined for gamma >= 0, as for Qmax.
+ * path_cap must be at least that bound, taken at M = N = the stacked length of max_len for the
+ * batch entry (floor(4 L / 3) - 2) and at the matrix' own M, N for acoss_path_crp_dmax:
+ * ACOSS_E_ARG otherwise, the message naming the bound. A stacked length, M or N above 65,535
+ * returns ACOSS_E_SHAPE, a non-binary matrix ACOSS_E_NONBINARY; a matrix with fewer than 3 rows
+ * or columns has score 0 and an empty path. */
+int acoss_crp_locate_dmax(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                          int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                          float* dmax_out, int32_t* seg_out, int32_t* oti_out, void* hip_stream);
+int acoss_locate_crp_dmax(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
+                          float* score_out, int32_t* seg_out, void* hip_stream);
+int acoss_crp_path_dmax(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                        int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                        float* dmax_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
+                        int32_t* path_out, void* hip_stream);
+int acoss_path_crp_dmax(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext, float* score_out,
+                        int32_t* seg_out, int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream);
 
 /* acoss smith_waterman_constrained (A8, acoss/algorithms/utils/alignment_tools.py:25-46) on
  * a batch of binary matrices: matrix b is (rows[b] x cols[b]) uint8 at byte offset off[b]
