@@ -70,6 +70,7 @@ SIGNATURES = {
     "acoss_snf_diffuse_rows": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp],
     "acoss_snf_left_rows": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, ctypes.c_double, _vp, _i32, _vp],
     "acoss_simple_mp": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
+    "acoss_simple_profile": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "acoss_median_downsample": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "acoss_simple_features": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp],
     "acoss_earlyfusion": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, ctypes.c_double,
@@ -654,6 +655,60 @@ def simple_mp(feats, pairs, sslen=10, apply_oti=True):
             raise ValueError("SiMPle features are (12, n) blocks")
     flat, off, _, cols, _, _ = _pack_mats(mats, torch.float64)
     return simple_mp_packed(flat, off, cols, pairs, sslen, apply_oti)
+
+
+def simple_profile_offsets(track_len, pairs, sslen):
+    """Where each pair's matrix profile starts in the ragged output of simple_profile (host only,
+    pure numpy): int64 (P + 1,), pair p's rows at [off[p], off[p + 1]), as many as its query has
+    length-sslen subsequences, max(len[query] - sslen + 1, 0)."""
+    lens = np.asarray(track_len, np.int64).reshape(-1)
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if len(pairs) and (int(pairs.min()) < 0 or int(pairs.max()) >= len(lens)):
+        raise ValueError("pair indices must lie in [0, %d)" % len(lens))
+    off = np.zeros(len(pairs) + 1, np.int64)
+    np.cumsum(np.maximum(lens[pairs[:, 0]] - int(sslen) + 1, 0), out=off[1:])
+    return off
+
+
+def simple_profile_packed(flat, track_off, track_len, pairs, sslen=10, apply_oti=True):
+    """The SiMPle matrix profile and its index per ordered pair (acoss_simple_profile) over packed
+    (12 x n_t) float64 blocks, as simple_mp_packed takes them. Returns a dict of device tensors:
+    off i64 (P + 1,) (simple_profile_offsets), mp f64 and mpi i32 (off[-1],) ragged by off (row i
+    of pair p: its distance to the nearest reference subsequence and that subsequence's index; NaN
+    and -1 where a row has none), score f64 (P,) = median(mp) = simple_mp's, oti i32 (P,)."""
+    torch = _torch()
+    lib = load_library()
+    lens = np.asarray(track_len.cpu() if isinstance(track_len, torch.Tensor) else track_len, np.int64)
+    pairs, host_pairs = _pairs_dev(pairs, len(lens))
+    if host_pairs is None:
+        host_pairs = pairs.cpu().numpy()
+    P = pairs.shape[0]
+    off = simple_profile_offsets(lens, host_pairs, sslen)
+    total = int(off[-1])
+    mp = torch.empty(total, dtype=torch.float64, device="cuda")
+    mpi = torch.empty(total, dtype=torch.int32, device="cuda")
+    score = torch.empty(P, dtype=torch.float64, device="cuda")
+    oti = torch.empty(P, dtype=torch.int32, device="cuda")
+    flat_d = _dev(flat, torch.float64)
+    off_d = _dev(track_off, torch.int64)
+    len_d = _dev(lens.astype(np.int32), torch.int32)
+    poff_d = _dev(off, torch.int64)
+    rc = lib.acoss_simple_profile(_ptr(flat_d), _ptr(off_d), _ptr(len_d), len(lens), int(lens.max(initial=0)),
+                                  _ptr(pairs), int(P), int(sslen), int(bool(apply_oti)), _ptr(poff_d), total,
+                                  _ptr(mp), _ptr(mpi), _ptr(score), _ptr(oti), _stream())
+    _check(rc, "acoss_simple_profile")
+    return {"off": poff_d, "mp": mp, "mpi": mpi, "score": score, "oti": oti}
+
+
+def simple_profile(feats, pairs, sslen=10, apply_oti=True):
+    """simple_profile_packed for a list of (12, n) float64 arrays, as simple_mp takes them."""
+    torch = _torch()
+    mats = [np.asarray(f) if not isinstance(f, torch.Tensor) else f for f in feats]
+    for f in mats:
+        if f.shape[0] != 12:
+            raise ValueError("SiMPle features are (12, n) blocks")
+    flat, off, _, cols, _, _ = _pack_mats(mats, torch.float64)
+    return simple_profile_packed(flat, off, cols, pairs, sslen, apply_oti)
 
 
 def median_downsample(feats, track_off, track_len, factor=40):

@@ -7,12 +7,15 @@ ISMIR 2016.
 means, Hann smoothing, column L2 norm; the reference recomputes them for every pair,
 :120-126), and `similarity(idxs)` scores a chunk of ordered pairs with one acoss_simple_mp
 call (simple.hip: Simple.oti + matrix profile + median). Ds['main'][i, j] = -median(MP).
+`profile(idxs)` returns the matrix profile itself and its index per pair (acoss_simple_profile):
+which part of the reference each part of the query is nearest to.
 """
 import argparse
 
 import numpy as np
 
 from .. import _lib
+from ..engine import subsequence_frames
 from .algorithm_template import CoverAlgorithm
 
 __all__ = ["Simple"]
@@ -27,6 +30,7 @@ class Simple(CoverAlgorithm):
         self.chroma_type = chroma_type
         self.all_feats = {}
         self._packed = None
+        self._n_frames = None  # frames of chroma_type per song before the window means (prepare)
         CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name="SiMPle", datapath=datapath, shortname=shortname,
                                 cachedir=cachedir)
 
@@ -47,6 +51,7 @@ class Simple(CoverAlgorithm):
         if self._prepared:
             return
         chromas = [f[self.chroma_type] for f in self.load_features_many((self.chroma_type,))]
+        self._n_frames = np.array([len(c) for c in chromas], np.int64)
         out, out_off, T = self._features(chromas)
         host = out.cpu().numpy()
         for i in range(self.N):
@@ -78,6 +83,29 @@ class Simple(CoverAlgorithm):
         out, off, T = self._packed
         score, _ = _lib.simple_mp_packed(out, off, T, idxs.astype(np.int32), self.SSLEN)
         self.Ds['main'][idxs[:, 0], idxs[:, 1]] = -score.cpu().numpy()
+
+    def profile(self, idxs):
+        """The matrix profile of every (query, reference) pair of idxs and its index: a dict of
+        host arrays 'score' (P,) (Ds['main'] holds -score), 'oti' (P,), 'off' (P + 1,) int64, 'mp'
+        (total,) float64 and 'mpi' (total,) int32, and 'query_frames' / 'reference_frames'
+        (total, 2) int64. Row i of pair p sits at off[p] + i: mp is the distance of the query's
+        subsequence i (SSLEN feature columns from column i) to its nearest subsequence of the
+        reference, mpi that subsequence's first column (the smallest among equal distances; -1,
+        with NaN in mp, where there is none), and the frame arrays hold the half-open ranges the
+        two cover in frames of `chroma_type` before the window means (engine.subsequence_frames;
+        the reference's is (-1, -1) where mpi is -1). Not collective: a rank profiles the pairs it
+        is given."""
+        self.prepare()
+        idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
+        out, off, T = self._packed
+        r = {k: v.cpu().numpy() for k, v in _lib.simple_profile_packed(out, off, T, idxs, self.SSLEN).items()}
+        rows = np.diff(r["off"])
+        i = np.arange(r["off"][-1]) - np.repeat(r["off"][:-1], rows)
+        r["query_frames"] = subsequence_frames(i, self.SSLEN, self.WIN, self.SKIP,
+                                               np.repeat(self._n_frames[idxs[:, 0]], rows))
+        r["reference_frames"] = subsequence_frames(r["mpi"], self.SSLEN, self.WIN, self.SKIP,
+                                                   np.repeat(self._n_frames[idxs[:, 1]], rows))
+        return r
 
     def _device_scores(self, idxs):
         """-median(MP) per ordered pair as float32 device scores (the memmap's dtype)."""

@@ -44,6 +44,21 @@ def path_frames(cells, tau, factor):
     return np.asarray(cells, np.int64).reshape(-1, 2) * (int(tau) * int(factor))
 
 
+def subsequence_frames(idx, sslen, win, skip, n_frames):
+    """SiMPle subsequence indices -> half-open ranges of original feature frames (pure numpy).
+    idx: (n,) subsequence indices (rows of a matrix profile, or its index entries); n_frames: (n,)
+    (or scalar) frame counts of the tracks before the window means. SiMPle column c is the mean of
+    the original frames [c*skip, min(c*skip + win, n)) (simple_silva.py:38-41) and subsequence i
+    the columns i .. i + sslen - 1, so its range is [i*skip, min((i + sslen - 1)*skip + win, n)).
+    Returns (n, 2) int64; an index of -1 (no nearest subsequence) maps to (-1, -1), as an empty
+    segment does in segment_frames."""
+    idx = np.asarray(idx, np.int64).reshape(-1)
+    n = np.broadcast_to(np.asarray(n_frames, np.int64), idx.shape)
+    r = np.stack([idx * skip, np.minimum((idx + sslen - 1) * skip + win, n)], 1)
+    r[idx < 0] = -1
+    return r
+
+
 class ChromaBank:
     """12-bin chroma of a whole corpus resident on the current GPU."""
 

@@ -30,6 +30,11 @@
 // minimum per step, one LDS atomic per row per wave. Per track: a frame-major query copy with
 // the 12 bins stored twice (the OTI pairing is the scalar load at bin offset k) and a reference
 // copy of 128-B records (12 bins + 4 pad). The median is a bitonic sort of the row minima in LDS.
+//
+// acoss_simple_profile returns the row minima themselves (the matrix profile) and the smallest
+// column attaining each (the profile index): the PROF = 1 instantiations of k_simple_mfma (L = 10)
+// and k_simple_pair (other L) walk a pair twice, the second time comparing every distance with its
+// row's minimum. The PROF = 0 instantiations are the score kernels, instruction for instruction.
 #include "common.hpp"
 
 namespace acoss {
@@ -177,16 +182,32 @@ __global__ void k_simple_track(const double* __restrict__ feats, const int64_t* 
   }
 }
 
+// What the profile instantiations of the pair kernels write besides the score: the profile and its
+// index, ragged by off (acoss_simple_profile). The score instantiations carry an empty struct.
+template <int PROF>
+struct ProfOut {};
+template <>
+struct ProfOut<1> {
+  const int64_t* off;  // prof_off of the launch's first pair
+  double* mp;
+  int32_t* mpi;
+};
+
 // Generic sslen (1..16): one thread per diagonal, L-deep shift register of G.
+// PROF = 1 also returns the row minima and their columns: the diagonal walk runs a second time
+// (mode 1) and every distance equal to its row's minimum offers its column to an LDS atomicMin on
+// mpi_s[row] (the same IEEE operations in the same order as in mode 0, so equality is exact).
+template <int PROF>
 __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ feats, const int64_t* __restrict__ off,
                                                      const int32_t* __restrict__ len, const int32_t* __restrict__ pairs,
                                                      const double* __restrict__ prof, const double* __restrict__ wnorm,
                                                      const int64_t* __restrict__ toff, int L, int apply_oti,
                                                      double* __restrict__ score,
-                                                     int32_t* __restrict__ oti_out) {
+                                                     int32_t* __restrict__ oti_out, ProfOut<PROF> po) {
   __shared__ double sa[kMaxLen];
   __shared__ double sb[kMaxLen];
   __shared__ unsigned long long mpk[kMaxLen];
+  __shared__ int32_t mpi_s[PROF ? kMaxLen : 1];  // PROF: the smallest column at each row's minimum
   __shared__ int s_k;
   __shared__ double s_med[2];
   const int p = blockIdx.x;
@@ -203,11 +224,17 @@ __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ 
   }
   if (P <= 0 || Q <= 0) {
     if (t == 0) score[p] = __builtin_nan("");
+    if constexpr (PROF)
+      for (int i = t; i < P; i += 256) {  // rows without a distance: the untouched key's NaN, no column
+        po.mp[po.off[p] + i] = dkey_inv(~0ull);
+        po.mpi[po.off[p] + i] = -1;
+      }
     return;
   }
   for (int i = t; i < P; i += 256) {
     sa[i] = wnorm[toff[ta] + i];
     mpk[i] = ~0ull;
+    if constexpr (PROF) mpi_s[i] = INT32_MAX;
   }
   __syncthreads();
   const int k = s_k;
@@ -216,6 +243,11 @@ __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ 
   for (int c = 0; c < 12; ++c) rowA[c] = ((c + k) % 12) * na;
   for (int j = t; j < Q; j += 256) sb[j] = wnorm[toff[tb] + j];  // a roll keeps the norms
   __syncthreads();
+  // mode 0: the row minima; mode 1 (PROF): their columns. The score instantiation has no second
+  // trip and, the condition being a constant, no loop at all; the profile one is unrolled
+  int mode = 0;
+#pragma unroll
+  do {
   for (int dg = t; dg < P + Q - 1; dg += 256) {
     const int o = dg - (P - 1);  // j - i
     const int r0 = o < 0 ? -o : 0;
@@ -238,11 +270,23 @@ __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ 
         for (int u = 0; u < kMaxL; ++u)
           if (u >= kMaxL - L) qt = qt + buf[u];
         const double dist = (sb[r + o] + sa[r]) - 2.0 * qt;
-        atomicMin(&mpk[r], dkey(dist));
+        if (mode == 0) {
+          atomicMin(&mpk[r], dkey(dist));
+        } else if constexpr (PROF) {
+          // an untouched key decodes to NaN and equals nothing; the plain read of mpi_s only
+          // filters (the value never grows), so a track of ties issues few atomics
+          if (dist == dkey_inv(mpk[r]) && r + o < mpi_s[r]) atomicMin(&mpi_s[r], r + o);
+        }
       }
     }
   }
   __syncthreads();
+  } while (PROF && ++mode < 2);
+  if constexpr (PROF)
+    for (int i = t; i < P; i += 256) {
+      po.mp[po.off[p] + i] = dkey_inv(mpk[i]);
+      po.mpi[po.off[p] + i] = mpi_s[i] == INT32_MAX ? -1 : mpi_s[i];
+    }
   // median: the order statistics P/2 (and P/2 - 1 for even P) by exact rank counting
   const int k_hi = P / 2, k_lo = (P % 2) ? P / 2 : P / 2 - 1;
   for (int e = t; e < P; e += 256) {
@@ -552,30 +596,63 @@ constexpr int kGT = kDW / 16 + 1;        // 16 x 16 tiles per 16-step block
 constexpr int kGS = kDW + 17;            // LDS row stride in doubles: (kGS - 1) * 2 = 32 mod 64 banks
 typedef double f64x4m __attribute__((ext_vector_type(4)));
 
+// PROF = 1 also returns the profile and its index (mpk_g is unused). The keys of the row
+// minima land in the pair's own range of po.mp (P keys, decoded in place at the end) instead of a
+// workspace slot, and after a block-wide barrier the pair is walked a second time (mode 1): the
+// same loads, MFMAs and window sums in the same order, so every distance has the bits it had in
+// the first walk, without the reduce-scatter; a distance equal to its row's minimum (wave-uniform:
+// the block's 16 minima sit in 16 lanes and are read by readlane) offers its column to
+// atomicMin(&mpi[row]). Lanes own increasing diagonals, so of a wave's matching lanes the lowest,
+// and its lowest k, holds the wave's smallest column: one ballot per step, at most one atomic per
+// row and wave group, however many distances tie.
+template <int PROF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_simple_mfma(
     const double* __restrict__ ext, const double* __restrict__ rec, const int32_t* __restrict__ len,
     const int32_t* __restrict__ pairs, const double* __restrict__ prof, const double* __restrict__ wpad,
     const int64_t* __restrict__ woff, const int64_t* __restrict__ toff, int n2max, int64_t n_pairs, int apply_oti,
-    unsigned long long* __restrict__ mpk_g, double* __restrict__ score, int32_t* __restrict__ oti_out) {
+    unsigned long long* __restrict__ mpk_g, double* __restrict__ score, int32_t* __restrict__ oti_out,
+    ProfOut<PROF> po) {
   constexpr int L = kFastL;
   extern __shared__ double gsm[];  // 4 waves x 16 x kGS doubles; reused for the final sort
   __shared__ int s_k;
   const int t = threadIdx.x;
-  const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  int lane = t & 63;  // re-read per walk below
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int64_t p = blockIdx.x;
   if (p >= n_pairs) return;  // whole block
   const int ta = pairs[2 * p], tb = pairs[2 * p + 1];
   const int na = len[ta], nb = len[tb];
   const int P = na - L + 1, Q = nb - L + 1;
   const bool live = P > 0 && Q > 0;
-  unsigned long long* mpk = mpk_g + (size_t)blockIdx.x * n2max;  // this launch's pair slot
+  // this launch's pair slot (PROF: the pair's own range of the profile) and the keys in it
+  unsigned long long* mpk;
+  int32_t* mpi = nullptr;
+  int nk;
+  if constexpr (PROF) {
+    mpk = reinterpret_cast<unsigned long long*>(po.mp + po.off[p]);
+    mpi = po.mpi + po.off[p];
+    nk = max(P, 0);
+  } else {
+    mpk = mpk_g + (size_t)blockIdx.x * n2max;
+    nk = n2max;
+  }
   if (t == 0) {
     const int best = simple_oti_index(prof + ta * 12, prof + tb * 12);
     s_k = apply_oti ? best : 0;
     if (oti_out) oti_out[p] = best;
     if (!live) score[p] = __builtin_nan("");
   }
-  for (int i = t; i < n2max; i += 256) mpk[i] = ~0ull;
+  if constexpr (PROF) {
+    if (!live) {  // rows without a distance: the untouched key's NaN, no column
+      for (int i = t; i < nk; i += 256) {
+        mpk[i] = __builtin_bit_cast(unsigned long long, dkey_inv(~0ull));
+        mpi[i] = -1;
+      }
+      return;
+    }
+    for (int i = t; i < nk; i += 256) mpi[i] = INT32_MAX;
+  }
+  for (int i = t; i < nk; i += 256) mpk[i] = ~0ull;
   __threadfence();
   __syncthreads();
   if (!live) return;  // whole block (uniform)
@@ -589,6 +666,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const int ND = P + Q - 1;
   const int NG = (ND + kDW - 1) / kDW;
   const double kInf = __builtin_inf();
+  // mode 0: the row minima into mpk; mode 1 (PROF): the smallest column attaining each of them
+  // (as in k_simple_pair: no loop in the score instantiation, each walk compiled for its own mode
+  // in the profile one)
+  int mode = 0;
+#pragma unroll
+  do {
+  // the second walk's lane constants are formed after the first walk (the compiler would hoist
+  // them above it, where no register is free: 3 VGPRs went to scratch)
+  if constexpr (PROF) {
+    if (mode == 1) asm volatile("" : "+v"(lane));
+  }
   const int li = lane & 15, lk = lane >> 4;  // MFMA operand row / k index
   for (int g = wave; g < NG; g += 4) {
     const int ob = -(P - 1) + g * kDW;  // diagonal of lane 0, k = 0
@@ -672,6 +760,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
       const int i0 = x0 - (L - 1) + yl;
       const double sa_l = san;
       san = Wa[x0 + 16 + (lane & 15) - (L - 1)];
+      // mode 1: lane s (mod 16) holds the minimum of the row step s completes; NaN, which equals no
+      // distance, outside the rows this group emits and where no distance was below +inf
+      double rmn_l = 0.0;
+      if (PROF && mode == 1) {
+        const int rr = x0 + (lane & 15) - (L - 1);
+        rmn_l = __builtin_nan("");
+        if ((lane & 15) < send && rr >= 0 && rr < P)
+          rmn_l = dkey_inv(__hip_atomic_load(&mpk[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      }
       // the dots of steps 0..7 now, of steps 8..15 at step kP0 (before the first store into G:
       // LDS ops of one wave run in order), so only half of them are live through the first steps
       constexpr int kP0 = 16 - kGT - 1;  // step of block b + 1's tile 0 (its last tile stored at step 15)
@@ -709,10 +806,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(__builtin_bit_cast(unsigned long long, sa_l) >> 32), s) << 32) |
             (unsigned)__builtin_amdgcn_readlane((int)(unsigned)__builtin_bit_cast(unsigned long long, sa_l), s));
         double m = kInf;
+        if (mode == 0) {
 #pragma unroll
-        for (int k = 0; k < kKM; ++k) {
-          const double qt = W[k][L - 1] + gall[s][k];
-          m = vmin_f64(m, fma(-2.0, qt, sbv[s + k] + sar));
+          for (int k = 0; k < kKM; ++k) {
+            const double qt = W[k][L - 1] + gall[s][k];
+            m = vmin_f64(m, fma(-2.0, qt, sbv[s + k] + sar));
+          }
+        } else {
+          const double rmn = __builtin_bit_cast(double,
+              ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(__builtin_bit_cast(unsigned long long, rmn_l) >> 32), s) << 32) |
+              (unsigned)__builtin_amdgcn_readlane((int)(unsigned)__builtin_bit_cast(unsigned long long, rmn_l), s));
+          int khit = kKM;  // this lane's lowest diagonal whose distance equals the row minimum
+#pragma unroll
+          for (int k = kKM - 1; k >= 0; --k) {
+            const double qt = W[k][L - 1] + gall[s][k];
+            if (fma(-2.0, qt, sbv[s + k] + sar) == rmn) khit = k;
+          }
+          const unsigned long long hits = __builtin_amdgcn_ballot_w64(khit < kKM);
+          // a hit implies a row in [0, P) (rmn is NaN elsewhere) and a column in [0, Q) (sbv is +inf elsewhere)
+          if (hits != 0 && lane == __builtin_ctzll(hits)) atomicMin(&mpi[x0 + s - (L - 1)], i0 + s + khit);
         }
 #pragma unroll
         for (int k = 0; k < kKM; ++k) {
@@ -724,20 +836,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         if (s == 15) sbv[16] = Wb[i0 + 32];
         // reduce-scatter of the 16 step minima over the 64 lanes, as the steps complete
         mv[s] = m;
-        if (s & 1) {  // lanes l, l ^ 32: lanes < 32 keep step s - 1, the others step s
+        if (mode == 0 && (s & 1)) {  // lanes l, l ^ 32: lanes < 32 keep step s - 1, the others step s
           double x = mv[s - 1], y = mv[s];
           swap32_f64(x, y);
           ra[s >> 1] = vmin_f64(x, y);
         }
-        if ((s & 3) == 3) {  // lanes l, l ^ 16
+        if (mode == 0 && (s & 3) == 3) {  // lanes l, l ^ 16
           double x = ra[(s >> 1) - 1], y = ra[s >> 1];
           swap16_f64(x, y);
           rb[s >> 2] = vmin_f64(x, y);
         }
-        if ((s & 7) == 7) rc[s >> 3] = xpair_min<8>(rb[(s >> 2) - 1], rb[s >> 2], lane);  // lanes l, l ^ 8
+        if (mode == 0 && (s & 7) == 7) rc[s >> 3] = xpair_min<8>(rb[(s >> 2) - 1], rb[s >> 2], lane);  // lanes l, l ^ 8
         if (tt >= 1 && tt <= kGT) store_tile(acc[tt - 1], tt - 1);  // a step after its MFMAs (their latency)
         __builtin_amdgcn_sched_barrier(0);    // one step per scheduling region: no tile's MFMAs hoisted
       }
+      if (mode == 0) {
       double v = xpair_min<4>(rc[0], rc[1], lane);  // lanes l, l ^ 4
       v = vmin_f64(v, dpp_f64<0x4E>(v));               // quad_perm [2,3,0,1]: l ^ 2
       v = vmin_f64(v, dpp_f64<0xB1>(v));               // quad_perm [1,0,3,2]: l ^ 1
@@ -745,13 +858,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
       const int step = 8 * ((lane >> 2) & 1) + 4 * ((lane >> 3) & 1) + 2 * ((lane >> 4) & 1) + ((lane >> 5) & 1);
       const int r = x0 + step - (L - 1);
       if ((lane & 3) == 0 && step < send && r >= 0 && r < P && v < kInf) atomicMin(&mpk[r], dkey(v));
+      }
     }
   }
   __threadfence();
-  __syncthreads();  // every wave's atomics complete
+  __syncthreads();  // every wave's atomics complete (mode 1: the columns are in mpi, and G is free)
+  } while (PROF && ++mode < 2);
   // the row-minimum keys into LDS, then the bitonic sort and the median as k_simple_diag
   unsigned long long* sk = reinterpret_cast<unsigned long long*>(gsm);
-  for (int i = t; i < n2max; i += 256) sk[i] = __hip_atomic_load(&mpk[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (PROF) {
+    // pads sort last; the pair's keys are decoded in place (mp_out) once their copy is taken
+    for (int i = t; i < n2max; i += 256) {
+      const unsigned long long key =
+          i < nk ? __hip_atomic_load(&mpk[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
+      sk[i] = key;
+      if (i < nk) {
+        mpk[i] = __builtin_bit_cast(unsigned long long, dkey_inv(key));
+        if (__hip_atomic_load(&mpi[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == INT32_MAX) mpi[i] = -1;
+      }
+    }
+  } else {
+    for (int i = t; i < n2max; i += 256) sk[i] = __hip_atomic_load(&mpk[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   __syncthreads();
   for (int kk = 2; kk <= n2max; kk <<= 1) {
     for (int j = kk >> 1; j > 0; j >>= 1) {
@@ -772,10 +900,87 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   if (t == 0) score[p] = (P % 2) ? dkey_inv(sk[P / 2]) : 0.5 * (dkey_inv(sk[P / 2 - 1]) + dkey_inv(sk[P / 2]));
 }
 
+// prof_off against the pairs' own profile lengths, before any profile write: the first pair whose
+// range is negative, too short or past prof_total goes to bad[0] (preset to the largest value)
+__global__ void k_simple_prof_check(const int32_t* __restrict__ len, const int32_t* __restrict__ pairs, int64_t n_pairs,
+                                    int L, const int64_t* __restrict__ prof_off, int64_t prof_total,
+                                    unsigned long long* __restrict__ bad) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  const int64_t P = max(len[pairs[2 * p]] - L + 1, 0);
+  const int64_t lo = prof_off[p], hi = prof_off[p + 1];
+  if (lo < 0 || hi < lo || hi > prof_total || P > hi - lo) atomicMin(bad, (unsigned long long)p);
+}
+
 int pow2_at_least(int v) {
   int p = 2;
   while (p < v) p <<= 1;
   return p;
+}
+
+// The per-track tables of one call, shared by acoss_simple_mp and acoss_simple_profile.
+// Workspace slot 8: prof | toff | woff | used | total; slot 13: fnorm, wnorm and, on the fast path,
+// ext and rec, each packed by toff (the call's tracks only, at their own lengths: 336 B per frame
+// on the fast path, 16 B otherwise), then the padded window norms of the MFMA kernel.
+// With prof_off (acoss_simple_profile) the ranges are checked on the device as well and
+// *bad_pair, the first offending pair or -1, comes back in the read-back of the track scan.
+struct SimpleTracks {
+  double *prof, *wnorm, *ext, *rec, *wpad;
+  int64_t *toff, *woff;
+};
+
+int simple_tracks(const double* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                  const int32_t* pairs, int64_t n_pairs, int32_t sslen, bool fast, bool mfma, const int64_t* prof_off,
+                  int64_t prof_total, int64_t* bad_pair, hipStream_t s, SimpleTracks* out) {
+  const size_t prof_bytes = align_up((size_t)n_tracks * 12 * 8, 256);
+  const size_t toff_bytes = align_up((size_t)n_tracks * 8, 256);
+  const size_t used_bytes = align_up((size_t)n_tracks * 4, 256);
+  const size_t head = prof_bytes + 2 * toff_bytes + used_bytes + 256;
+  char* hd = static_cast<char*>(workspace(8, head));
+  if (!hd) return ACOSS_E_HIP;
+  double* prof = reinterpret_cast<double*>(hd);
+  int64_t* toff = reinterpret_cast<int64_t*>(hd + prof_bytes);
+  int64_t* woff = reinterpret_cast<int64_t*>(hd + prof_bytes + toff_bytes);
+  int32_t* used = reinterpret_cast<int32_t*>(hd + prof_bytes + 2 * toff_bytes);
+  int64_t* d_total = reinterpret_cast<int64_t*>(hd + prof_bytes + 2 * toff_bytes + used_bytes);
+  ACOSS_HIP_CHECK(hipMemsetAsync(used, 0, used_bytes, s));
+  hipLaunchKernelGGL(k_simple_mark, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, pairs, n_pairs, used);
+  ACOSS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_simple_scan, dim3(1), dim3(1024), 0, s, track_len, used, n_tracks, toff, woff, d_total);
+  ACOSS_LAUNCH_CHECK();
+  if (prof_off) {
+    ACOSS_HIP_CHECK(hipMemsetAsync(d_total + 2, 0xff, 8, s));
+    hipLaunchKernelGGL(k_simple_prof_check, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, track_len, pairs,
+                       n_pairs, sslen, prof_off, prof_total, reinterpret_cast<unsigned long long*>(d_total + 2));
+    ACOSS_LAUNCH_CHECK();
+  }
+  int64_t tot[3] = {0, 0, -1};  // frames, flagged tracks, first pair with a bad profile range
+  ACOSS_HIP_CHECK(hipMemcpyAsync(tot, d_total, prof_off ? 24 : 16, hipMemcpyDeviceToHost, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  if (bad_pair) *bad_pair = tot[2];
+  if (tot[2] >= 0) return ACOSS_OK;  // the caller refuses: nothing else is built or written
+  const int64_t frames = tot[0];
+  const size_t vec_bytes = align_up((size_t)std::max<int64_t>(frames, 8) * 8, 256);
+  const int64_t wpad_n = mfma ? frames + (int64_t)kWPad * (tot[1] + 1) : 0;
+  const size_t wpad_bytes = align_up((size_t)wpad_n * 8, 256);
+  const size_t bytes = 2 * vec_bytes + (fast ? vec_bytes * (kExt + kRec) : 0) + wpad_bytes;
+  char* ws = static_cast<char*>(workspace(13, bytes));
+  if (!ws) return ACOSS_E_HIP;
+  double* fnorm = reinterpret_cast<double*>(ws);
+  double* wnorm = reinterpret_cast<double*>(ws + vec_bytes);
+  double* ext = reinterpret_cast<double*>(ws + 2 * vec_bytes);
+  double* rec = reinterpret_cast<double*>(ws + 2 * vec_bytes + vec_bytes * kExt);
+  double* wpad = mfma ? reinterpret_cast<double*>(ws + 2 * vec_bytes + (fast ? vec_bytes * (kExt + kRec) : 0)) : nullptr;
+  if (mfma) {
+    hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)std::min<int64_t>((wpad_n + 255) / 256, 4096)), dim3(256), 0, s, wpad,
+                       wpad_n, __builtin_inf());
+    ACOSS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_simple_track, dim3(n_tracks), dim3(256), 0, s, feats, track_off, track_len, n_tracks, sslen,
+                     prof, fnorm, wnorm, ext, rec, toff, fast ? 1 : 0, wpad, woff);
+  ACOSS_LAUNCH_CHECK();
+  *out = SimpleTracks{prof, wnorm, ext, rec, wpad, toff, woff};
+  return ACOSS_OK;
 }
 
 }  // namespace
@@ -815,53 +1020,17 @@ extern "C" int acoss_simple_mp(const double* feats, const int64_t* track_off, co
   const bool fast = sslen == kFastL;
   const char* senv = getenv("ACOSS_SIMPLE_SH");
   const int sh = senv ? atoi(senv) : 1;
-  // per-track tables (workspace slot 8): prof | toff | used | total; slot 13: fnorm, wnorm and, on
-  // the fast path, ext and rec, each packed by toff (the call's tracks only, at their own lengths:
-  // 336 B per frame on the fast path, 16 B otherwise)
-  const size_t prof_bytes = align_up((size_t)n_tracks * 12 * 8, 256);
-  const size_t toff_bytes = align_up((size_t)n_tracks * 8, 256);
-  const size_t used_bytes = align_up((size_t)n_tracks * 4, 256);
   // the MFMA kernel (frame dots on v_mfma_f64_16x16x4_f64), bit-identical to the VALU kernels: the
   // default for tracks of >= 256 frames (the VALU kernels pack several short pairs per block:
   // 200 frames 6.8M vs 5.5M pairs/s; profiles/r06/simple_mfma/); ACOSS_SIMPLE_MFMA=0 / 1 forces either
   const char* menv = getenv("ACOSS_SIMPLE_MFMA");
   const bool mfma = fast && (menv ? menv[0] == '1' : max_len >= 256);
-  const size_t head = prof_bytes + 2 * toff_bytes + used_bytes + 256;
-  char* hd = static_cast<char*>(workspace(8, head));
-  if (!hd) return ACOSS_E_HIP;
-  double* prof = reinterpret_cast<double*>(hd);
-  int64_t* toff = reinterpret_cast<int64_t*>(hd + prof_bytes);
-  int64_t* woff = reinterpret_cast<int64_t*>(hd + prof_bytes + toff_bytes);
-  int32_t* used = reinterpret_cast<int32_t*>(hd + prof_bytes + 2 * toff_bytes);
-  int64_t* d_total = reinterpret_cast<int64_t*>(hd + prof_bytes + 2 * toff_bytes + used_bytes);
-  ACOSS_HIP_CHECK(hipMemsetAsync(used, 0, used_bytes, s));
-  hipLaunchKernelGGL(k_simple_mark, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, pairs, n_pairs, used);
-  ACOSS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_simple_scan, dim3(1), dim3(1024), 0, s, track_len, used, n_tracks, toff, woff, d_total);
-  ACOSS_LAUNCH_CHECK();
-  int64_t tot[2] = {0, 0};  // frames, flagged tracks
-  ACOSS_HIP_CHECK(hipMemcpyAsync(tot, d_total, 16, hipMemcpyDeviceToHost, s));
-  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
-  const int64_t frames = tot[0];
-  const size_t vec_bytes = align_up((size_t)std::max<int64_t>(frames, 8) * 8, 256);
-  const int64_t wpad_n = mfma ? frames + (int64_t)kWPad * (tot[1] + 1) : 0;
-  const size_t wpad_bytes = align_up((size_t)wpad_n * 8, 256);
-  const size_t bytes = 2 * vec_bytes + (fast ? vec_bytes * (kExt + kRec) : 0) + wpad_bytes;
-  char* ws = static_cast<char*>(workspace(13, bytes));
-  if (!ws) return ACOSS_E_HIP;
-  double* fnorm = reinterpret_cast<double*>(ws);
-  double* wnorm = reinterpret_cast<double*>(ws + vec_bytes);
-  double* ext = reinterpret_cast<double*>(ws + 2 * vec_bytes);
-  double* rec = reinterpret_cast<double*>(ws + 2 * vec_bytes + vec_bytes * kExt);
-  double* wpad = mfma ? reinterpret_cast<double*>(ws + 2 * vec_bytes + (fast ? vec_bytes * (kExt + kRec) : 0)) : nullptr;
-  if (mfma) {
-    hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)std::min<int64_t>((wpad_n + 255) / 256, 4096)), dim3(256), 0, s, wpad,
-                       wpad_n, __builtin_inf());
-    ACOSS_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_simple_track, dim3(n_tracks), dim3(256), 0, s, feats, track_off, track_len, n_tracks, sslen,
-                     prof, fnorm, wnorm, ext, rec, toff, fast ? 1 : 0, wpad, woff);
-  ACOSS_LAUNCH_CHECK();
+  SimpleTracks T;
+  const int trc = simple_tracks(feats, track_off, track_len, n_tracks, pairs, n_pairs, sslen, fast, mfma, nullptr, 0,
+                                nullptr, s, &T);
+  if (trc != ACOSS_OK) return trc;
+  double *prof = T.prof, *wnorm = T.wnorm, *ext = T.ext, *rec = T.rec, *wpad = T.wpad;
+  int64_t *toff = T.toff, *woff = T.woff;
   const int n2max = pow2_at_least(max(max_len - kFastL + 1, 2));
   const int sboff = n2max;
   const int slotsz = sboff + (int)align_up((size_t)max_len, 2);
@@ -893,13 +1062,13 @@ extern "C" int acoss_simple_mp(const double* feats, const int64_t* track_off, co
     unsigned long long* mpk_g =
         static_cast<unsigned long long*>(workspace(16, (size_t)std::min<int64_t>(per, n_pairs) * n2max * 8));
     if (!mpk_g) return ACOSS_E_HIP;
-    ACOSS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_simple_mfma),
+    ACOSS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_simple_mfma<0>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
     for (int64_t p0 = 0; p0 < n_pairs; p0 += per) {
       const int64_t np = std::min<int64_t>(n_pairs - p0, per);
-      hipLaunchKernelGGL(k_simple_mfma, dim3((unsigned)np), dim3(256), mlds, s, ext, rec, track_len, pairs + 2 * p0,
+      hipLaunchKernelGGL(k_simple_mfma<0>, dim3((unsigned)np), dim3(256), mlds, s, ext, rec, track_len, pairs + 2 * p0,
                          prof, wpad, woff, toff, n2max, np, apply_oti, mpk_g, score_out + p0,
-                         oti_out ? oti_out + p0 : nullptr);
+                         oti_out ? oti_out + p0 : nullptr, ProfOut<0>{});
       ACOSS_LAUNCH_CHECK();
     }
     prof_end(PH_SIMPLE, s);
@@ -921,9 +1090,78 @@ extern "C" int acoss_simple_mp(const double* feats, const int64_t* track_off, co
       hipLaunchKernelGGL(kern, dim3((unsigned)((np + ppb - 1) / ppb)), dim3(256), lds, s, ext, rec, track_len, pp, prof,
                          wnorm, toff, n2max, sboff, slotsz, rboff, ppb, np, apply_oti, so, oo);
     } else {
-      hipLaunchKernelGGL(k_simple_pair, dim3((unsigned)np), dim3(256), 0, s, feats, track_off, track_len, pp, prof,
-                         wnorm, toff, sslen, apply_oti, so, oo);
+      hipLaunchKernelGGL(k_simple_pair<0>, dim3((unsigned)np), dim3(256), 0, s, feats, track_off, track_len, pp, prof,
+                         wnorm, toff, sslen, apply_oti, so, oo, ProfOut<0>{});
     }
+    ACOSS_LAUNCH_CHECK();
+  }
+  prof_end(PH_SIMPLE, s);
+  return ACOSS_OK;
+}
+
+extern "C" int acoss_simple_profile(const double* feats, const int64_t* track_off, const int32_t* track_len,
+                                    int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                    int32_t sslen, int32_t apply_oti, const int64_t* prof_off, int64_t prof_total,
+                                    double* mp_out, int32_t* mpi_out, double* score_out, int32_t* oti_out,
+                                    void* hip_stream) {
+  clear_error();
+  if (n_tracks < 0 || n_pairs < 0 || prof_total < 0 ||
+      (n_pairs > 0 && (!feats || !track_off || !track_len || !pairs || !prof_off)) ||
+      (prof_total > 0 && (!mp_out || !mpi_out))) {
+    set_error("acoss_simple_profile: bad arguments");
+    return ACOSS_E_ARG;
+  }
+  if (sslen < 1 || sslen > kMaxL) {
+    set_error("acoss_simple_profile: sslen=%d outside [1, %d]", sslen, kMaxL);
+    return ACOSS_E_ARG;
+  }
+  if (max_len > kMaxLen) {
+    set_error("acoss_simple_profile: max_len=%d exceeds %d SiMPle frames", max_len, kMaxLen);
+    return ACOSS_E_SHAPE;
+  }
+  if (n_pairs == 0) return ACOSS_OK;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  prof_begin(PH_SIMPLE, s);
+  // one kernel per sslen, whatever the lengths: the MFMA kernel for the reference's SSLEN, the
+  // generic kernel otherwise (the ACOSS_SIMPLE_K / SH / PPB / RED / MFMA overrides choose among
+  // score kernels only)
+  const bool fast = sslen == kFastL;
+  SimpleTracks T;
+  int64_t bad = -1;
+  const int trc = simple_tracks(feats, track_off, track_len, n_tracks, pairs, n_pairs, sslen, fast, fast, prof_off,
+                                prof_total, &bad, s, &T);
+  if (trc != ACOSS_OK) return trc;
+  if (bad >= 0) {
+    set_error("acoss_simple_profile: prof_off of pair %lld is negative, leaves less than the pair's profile length "
+              "or ends past prof_total=%lld", (long long)bad, (long long)prof_total);
+    return ACOSS_E_ARG;
+  }
+  // the median's score is formed in any case; without score_out it goes to a workspace
+  if (!score_out) {
+    score_out = static_cast<double*>(workspace(16, (size_t)n_pairs * 8));
+    if (!score_out) return ACOSS_E_HIP;
+  }
+  // pairs per launch (one block each); ACOSS_SIMPLE_PROFILE_BATCH overrides it
+  const char* benv = getenv("ACOSS_SIMPLE_PROFILE_BATCH");
+  int64_t per = (int64_t)1 << 20;
+  if (benv && atoll(benv) >= 1) per = std::min<int64_t>(atoll(benv), per);
+  const int n2max = pow2_at_least(max(max_len - kFastL + 1, 2));
+  const size_t mlds = (size_t)4 * 16 * kGS * 8;
+  if (fast)
+    ACOSS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_simple_mfma<1>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
+  for (int64_t p0 = 0; p0 < n_pairs; p0 += per) {
+    const int64_t np = std::min<int64_t>(n_pairs - p0, per);
+    const int32_t* pp = pairs + 2 * p0;
+    int32_t* oo = oti_out ? oti_out + p0 : nullptr;
+    const ProfOut<1> po{prof_off + p0, mp_out, mpi_out};
+    if (fast)
+      hipLaunchKernelGGL(k_simple_mfma<1>, dim3((unsigned)np), dim3(256), mlds, s, T.ext, T.rec, track_len, pp, T.prof,
+                         T.wpad, T.woff, T.toff, n2max, np, apply_oti, (unsigned long long*)nullptr, score_out + p0, oo,
+                         po);
+    else
+      hipLaunchKernelGGL(k_simple_pair<1>, dim3((unsigned)np), dim3(256), 0, s, feats, track_off, track_len, pp, T.prof,
+                         T.wnorm, T.toff, sslen, apply_oti, score_out + p0, oo, po);
     ACOSS_LAUNCH_CHECK();
   }
   prof_end(PH_SIMPLE, s);

@@ -265,6 +265,43 @@ int acoss_simple_mp(const double* feats, const int64_t* track_off, const int32_t
                     int32_t max_len, const int32_t* pairs, int64_t n_pairs, int32_t sslen, int32_t apply_oti,
                     double* score_out, int32_t* oti_out, void* hip_stream);
 
+/* The SiMPle matrix profile itself and its index (Silva et al., ISMIR 2016): for every length-sslen
+ * subsequence of the query its distance to the nearest subsequence of the reference, and which
+ * one that is. Inputs and refusals as acoss_simple_mp (sslen in 1..16, ACOSS_E_ARG otherwise;
+ * max_len above 4096 returns ACOSS_E_SHAPE). For pair p = (a, b): P = len[a] - sslen + 1 rows,
+ * Q = len[b] - sslen + 1 columns. The profiles are ragged, not padded (their lengths are known
+ * before the call): pair p's occupies mp_out[prof_off[p] .. prof_off[p] + max(P, 0)) and the same
+ * range of mpi_out.
+ *
+ * The definition.
+ *   dist(i, j) is the canonical value of oracle/crp_oracle.cpp or_simple_sim, on the reference
+ *     rolled by the OTI index when apply_oti is set: a frame dot is the product of bin 0 followed by
+ *     the fma chain over the reference's own bins 1..11, frame norms likewise, window sums are
+ *     sequential adds over t = 0..sslen-1, dist = (sb[j] + sa[i]) - 2 qt.
+ *   mp[i] = min_j dist(i, j): the row minimum the score kernels form, bit for bit.
+ *   mpi[i] = the smallest j with dist(i, j) == mp[i] (an IEEE compare: the oracle loop's
+ *     `dist < mn` keeps the first of equal distances).
+ *   A row with no distance below +inf (NaN features under its window, or Q <= 0 while P > 0)
+ *     holds NaN in mp and -1 in mpi.
+ *   score_out[p] (may be NULL) = median(mp), acoss_simple_mp's score_out[p] bit for bit (NaN where
+ *     P <= 0 or Q <= 0); oti_out[p] (may be NULL) = acoss_simple_mp's.
+ * A pair's output does not depend on its place in the list; a pair listed twice fills both of its
+ * ranges identically.
+ *
+ * prof_off: device int64[n_pairs + 1], checked on the device before any profile write: for every
+ * pair prof_off[p] >= 0, prof_off[p] + max(P, 0) <= prof_off[p + 1] and prof_off[p + 1] <=
+ * prof_total (the element count of mp_out and of mpi_out). Otherwise ACOSS_E_ARG, the message
+ * naming the first such pair, and nothing is written. (The check rides on the stream
+ * synchronisation acoss_simple_mp has as well.)
+ * Kernels (simple.hip): k_simple_mfma<1> for sslen = 10 at every length, k_simple_pair<1> for every
+ * other sslen; each walks the pair twice, the second time comparing every distance with its row's
+ * minimum. The ACOSS_SIMPLE_K / SH / PPB / RED / MFMA overrides do not apply; a launch takes up to
+ * 2^20 pairs, or ACOSS_SIMPLE_PROFILE_BATCH pairs if that is set lower. */
+int acoss_simple_profile(const double* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                         int32_t max_len, const int32_t* pairs, int64_t n_pairs, int32_t sslen, int32_t apply_oti,
+                         const int64_t* prof_off, int64_t prof_total, double* mp_out, int32_t* mpi_out,
+                         double* score_out, int32_t* oti_out, void* hip_stream);
+
 /* Per-track median downsampling of chroma (A13: Serra09/ChenFusion.load_features,
  * acoss/algorithms/rqa_serra09.py:44-53 and latefusion_chen.py:46-56, which call
  * librosa.util.sync(chroma.T, arange(0, n, factor), aggregate=np.median)).
