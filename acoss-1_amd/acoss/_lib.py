@@ -58,6 +58,8 @@ SIGNATURES = {
                             _vp, _vp],
     "acoss_path_crp_dmax": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp, _vp, _vp],
     "acoss_sw_constrained": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "acoss_sw_locate": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "acoss_sw_path": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp],
     "acoss_csm": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "acoss_get_oti": [_vp, _vp, _i32, _vp, _vp],
     "acoss_binarize_rows": [_vp, _i32, _i32, _i32, _vp, _vp],
@@ -75,6 +77,10 @@ SIGNATURES = {
     "acoss_simple_features": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp],
     "acoss_earlyfusion": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, ctypes.c_double,
                           _i32, _f32, _vp, _vp],
+    "acoss_earlyfusion_locate": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64,
+                                 ctypes.c_double, _i32, _f32, _vp, _vp, _vp],
+    "acoss_earlyfusion_path": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, ctypes.c_double,
+                               _i32, _f32, _vp, _vp, _i32, _vp, _vp, _vp],
     "acoss_ef_block_features": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                 _vp, _vp],
     "acoss_ftm2d_shingles": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, ctypes.c_double, ctypes.c_double, _vp, _vp],
@@ -433,6 +439,64 @@ def sw_constrained(mats):
 
 
 CSM_KINDS = {"euclidean": 0, "euclid": 0, "cosine": 1, "ssm": 2}
+
+
+def sw_path_bound(M, N):
+    """The most cells a constrained Smith-Waterman path of an (M, N) matrix can have: its cells lie in
+    [2, M - 2] x [2, N - 2] and climb in both coordinates (include/acoss_hip.h, acoss_sw_locate)."""
+    return max(0, min(int(M), int(N)) - 3)
+
+
+def sw_locate(mats):
+    """smith_waterman_constrained of a list of binary matrices with where its alignment lies
+    (acoss_sw_locate): device tensors {"score" (n,) f64, sw_constrained's bit for bit, "seg" (n, 4) i32 =
+    (r0, c0, r1, c1), the first and last cell of the path in the matrix's own rows and columns,
+    (-1, -1, -1, -1) where the score is 0}."""
+    torch = _torch()
+    mats = [_as_binary_u8(m) for m in mats]
+    out = {"score": _empty("float64", len(mats)), "seg": _empty("int32", len(mats), 4)}
+    if not mats:
+        return out
+    flat, off, rows, cols, mr, mc = _pack_mats(mats, torch.uint8)
+    rc = load_library().acoss_sw_locate(_ptr(flat), _ptr(off), _ptr(rows), _ptr(cols), len(mats), mr, mc,
+                                        _ptr(out["score"]), _ptr(out["seg"]), _stream())
+    if rc == -4:
+        raise IOError("Non-binary elements found in input")
+    _check(rc, "acoss_sw_locate")
+    return out
+
+
+def sw_path(mats, path_cap=None):
+    """sw_locate with the whole path (acoss_sw_path): {"score", "seg", "path_off" (n + 1,) i64, "cells"
+    (total, 2) i32}; the path of matrix k is cells[path_off[k]:path_off[k + 1]], (r, c) from (r0, c0)
+    to (r1, c1) in steps (1, 1), (2, 1), (1, 2), empty where the score is 0. path_cap: entries per
+    matrix of the padded buffer handed to the library, sw_path_bound of the largest rows and columns
+    unless given (a smaller one is refused). The matrices go to the library in chunks whose padded
+    output and direction planes stay near PATH_CHUNK_BYTES; each is compacted on the device."""
+    torch = _torch()
+    lib = load_library()
+    mats = [_as_binary_u8(m) for m in mats]
+    n = len(mats)
+    score, seg, lens = _empty("float64", n), _empty("int32", n, 4), _empty("int32", n)
+    mr = max([int(m.shape[0]) for m in mats], default=0)
+    mc = max([int(m.shape[1]) for m in mats], default=0)
+    cap = max(1, sw_path_bound(mr, mc)) if path_cap is None else int(path_cap)
+    chunk = max(1, PATH_CHUNK_BYTES // (8 * max(1, cap) + mr * mc // 4 + 1))
+    parts = []
+    for a in range(0, n, chunk):
+        k = min(chunk, n - a)
+        flat, off, rows, cols, _, _ = _pack_mats(mats[a:a + k], torch.uint8)
+        padded = torch.empty((k, max(1, cap), 2), dtype=torch.int32, device="cuda")
+        rc = lib.acoss_sw_path(_ptr(flat), _ptr(off), _ptr(rows), _ptr(cols), k, mr, mc, _ptr(score[a:a + k]),
+                               _ptr(seg[a:a + k]), cap, _ptr(lens[a:a + k]), _ptr(padded), _stream())
+        if rc == -4:
+            raise IOError("Non-binary elements found in input")
+        _check(rc, "acoss_sw_path")
+        parts.append(_compact_paths(lens[a:a + k], padded)[1])
+    path_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    path_off[1:] = torch.cumsum(lens.to(torch.int64), 0)
+    cells = torch.cat(parts) if parts else torch.empty((0, 2), dtype=torch.int32, device="cuda")
+    return {"score": score, "seg": seg, "path_off": path_off, "cells": cells}
 
 
 def csm(X, Y=None, kind="euclidean", oti_shift=0):
@@ -798,6 +862,32 @@ def _check_ef_neighbours(bank, pairs, kappa, K):
         raise err
 
 
+def _ef_band_order(pairs, T):
+    """The order acoss_earlyfusion and its locate / path forms run a large pair list in (a permutation of
+    range(P), device int64), or None for 4096 pairs or fewer.
+    Pairs in (reference band, query) order: a band of 16 reference tracks' block rows stays
+    cache-resident while every query track's rows stream past it once per band (an i-major
+    pair list streams every reference track's rows once per query). Results go back to the
+    caller's order. Da-TACOS shape, 15,000 songs: 3.29M -> 4.07M pairs/s (bands of 16..128
+    alike; profiles/r05/ef_short/efband15k_*.log). The runs holding the whole band come
+    first, so they start at multiples of 16 and the CSM kernel's groups of 64 pairs hold
+    four queries with the same 16 references (k_ef_csm_pack packs their rows and columns;
+    profiles/r06/ef_pack/README.txt). No host synchronisation: run lengths by scatter_add."""
+    torch = _torch()
+    P = pairs.shape[0]
+    if P <= 4096:
+        return None
+    band = 16
+    key = (pairs[:, 1].to(torch.int64) // band) * T + pairs[:, 0].to(torch.int64)
+    order = torch.argsort(key, stable=True)
+    ks = key[order]
+    start = torch.ones(P, dtype=torch.bool, device=ks.device)
+    start[1:] = ks[1:] != ks[:-1]
+    rid = torch.cumsum(start, 0) - 1
+    runlen = torch.zeros(P, dtype=torch.int64, device=ks.device).scatter_add_(0, rid, torch.ones_like(rid))[rid]
+    return order[torch.argsort((runlen < band).to(torch.int8), stable=True)]
+
+
 def earlyfusion(bank, pairs, kappa=0.1, K=10, mu=0.5):
     """Batched EarlyFusion scores (earlyfusion_traile.py:157-198). bank: dict of device tensors
     'mfccs', 'ssms', 'chromas' (sum nb x d, float32), 'chroma_med' (T x 12), 'off' (T,) int64,
@@ -812,25 +902,8 @@ def earlyfusion(bank, pairs, kappa=0.1, K=10, mu=0.5):
         return out
     _check_ef_neighbours(bank, pairs if host is None or "nb_host" not in bank else host, kappa, K)
     T = int(bank["nb"].shape[0])
-    order = None
-    if P > 4096:
-        # pairs in (reference band, query) order: a band of 16 reference tracks' block rows stays
-        # cache-resident while every query track's rows stream past it once per band (an i-major
-        # pair list streams every reference track's rows once per query). Scores go back to the
-        # caller's order. Da-TACOS shape, 15,000 songs: 3.29M -> 4.07M pairs/s (bands of 16..128
-        # alike; profiles/r05/ef_short/efband15k_*.log). The runs holding the whole band come
-        # first, so they start at multiples of 16 and the CSM kernel's groups of 64 pairs hold
-        # four queries with the same 16 references (k_ef_csm_pack packs their rows and columns;
-        # profiles/r06/ef_pack/README.txt). No host synchronisation: run lengths by scatter_add.
-        band = 16
-        key = (pairs[:, 1].to(torch.int64) // band) * T + pairs[:, 0].to(torch.int64)
-        order = torch.argsort(key, stable=True)
-        ks = key[order]
-        start = torch.ones(P, dtype=torch.bool, device=ks.device)
-        start[1:] = ks[1:] != ks[:-1]
-        rid = torch.cumsum(start, 0) - 1
-        runlen = torch.zeros(P, dtype=torch.int64, device=ks.device).scatter_add_(0, rid, torch.ones_like(rid))[rid]
-        order = order[torch.argsort((runlen < band).to(torch.int8), stable=True)]
+    order = _ef_band_order(pairs, T)
+    if order is not None:
         pairs = pairs[order].contiguous()
     dst = out if order is None else torch.empty_like(out)
     rc = lib.acoss_earlyfusion(_ptr(bank["mfccs"]), _ptr(bank["ssms"]), _ptr(bank["chromas"]), _ptr(bank["chroma_med"]),
@@ -841,6 +914,84 @@ def earlyfusion(bank, pairs, kappa=0.1, K=10, mu=0.5):
     if order is not None:
         out[order] = dst
     return out
+
+
+def _ef_args(bank, pairs, kappa, K, mu):
+    """The arguments acoss_earlyfusion and its locate / path forms share, after earlyfusion()'s checks:
+    (device pairs (P, 2) in the order they run in, that order (_ef_band_order) or None, the leading
+    arguments up to the feature widths, the trailing kappa, K, mu)."""
+    pairs, host = _pairs_dev(pairs, int(bank["nb"].shape[0]))
+    if pairs.shape[0]:
+        _check_ef_neighbours(bank, pairs if host is None or "nb_host" not in bank else host, kappa, K)
+    order = _ef_band_order(pairs, int(bank["nb"].shape[0]))
+    if order is not None:
+        pairs = pairs[order].contiguous()
+    lead = (_ptr(bank["mfccs"]), _ptr(bank["ssms"]), _ptr(bank["chromas"]), _ptr(bank["chroma_med"]),
+            _ptr(bank["off"]), _ptr(bank["nb"]), int(bank["nb"].shape[0]), int(bank["max_blocks"]),
+            int(bank["mfccs"].shape[1]), int(bank["ssms"].shape[1]), int(bank["chromas"].shape[1]))
+    return pairs, order, lead, (float(kappa), int(K), float(mu))
+
+
+def _unorder(order, t):
+    """A per-pair result of pairs run in `order` (None: as given), back in the caller's order."""
+    if order is None:
+        return t
+    out = t.new_empty(t.shape)
+    out[order] = t
+    return out
+
+
+def earlyfusion_locate(bank, pairs, kappa=0.1, K=10, mu=0.5):
+    """earlyfusion() with where each of the four alignments lies (acoss_earlyfusion_locate): device
+    tensors {"scores" (P, 4) f64, earlyfusion()'s bit for bit, "seg" (P, 4, 4) i32}: seg[p, s] =
+    (r0, c0, r1, c1), the first and last cell of the alignment in matrix s (mfccs, ssms, chromas,
+    early) of pair p, rows the query's blocks and columns the reference's, (-1, -1, -1, -1) where
+    the score is 0."""
+    pairs, order, lead, tail = _ef_args(bank, pairs, kappa, K, mu)
+    P = pairs.shape[0]
+    scores, seg = _empty("float64", P, 4), _empty("int32", P, 4, 4)
+    if P:
+        rc = load_library().acoss_earlyfusion_locate(*lead, _ptr(pairs), int(P), *tail, _ptr(scores), _ptr(seg),
+                                                     _stream())
+        _check(rc, "acoss_earlyfusion_locate")
+    return {"scores": _unorder(order, scores), "seg": _unorder(order, seg)}
+
+
+def earlyfusion_path(bank, pairs, kappa=0.1, K=10, mu=0.5):
+    """earlyfusion_locate with the four whole paths of every pair (acoss_earlyfusion_path): {"scores",
+    "seg", "path_off" (4 P + 1,) i64, "cells" (total, 2) i32}; the path of matrix s of pair p is
+    cells[path_off[4 p + s]:path_off[4 p + s + 1]], (query block, reference block) cells in steps
+    (1, 1), (2, 1), (1, 2). The pairs go to the library in chunks whose padded output stays near
+    PATH_CHUNK_BYTES; each is compacted on the device."""
+    torch = _torch()
+    lib = load_library()
+    pairs, order, lead, tail = _ef_args(bank, pairs, kappa, K, mu)
+    P = pairs.shape[0]
+    scores, seg, lens = _empty("float64", P, 4), _empty("int32", P, 4, 4), _empty("int32", P, 4)
+    cap = max(1, sw_path_bound(int(bank["max_blocks"]), int(bank["max_blocks"])))
+    chunk = max(1, PATH_CHUNK_BYTES // (4 * 8 * cap))
+    parts = []
+    for a in range(0, P, chunk):
+        n = min(chunk, P - a)
+        padded = torch.empty((4 * n, cap, 2), dtype=torch.int32, device="cuda")
+        rc = lib.acoss_earlyfusion_path(*lead, _ptr(pairs[a:a + n]), int(n), *tail, _ptr(scores[a:a + n]),
+                                        _ptr(seg[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded), _stream())
+        _check(rc, "acoss_earlyfusion_path")
+        parts.append(_compact_paths(lens[a:a + n].reshape(-1), padded)[1])
+    cells = torch.cat(parts) if parts else torch.empty((0, 2), dtype=torch.int32, device="cuda")
+    run_off = torch.zeros(4 * P + 1, dtype=torch.int64, device="cuda")  # in the order the pairs ran in
+    run_off[1:] = torch.cumsum(lens.reshape(-1).to(torch.int64), 0)
+    if order is None:
+        return {"scores": scores, "seg": seg, "path_off": run_off, "cells": cells}
+    # back to the caller's order: every cell moves by the shift of its matrix' first cell
+    lens_o = _unorder(order, lens).reshape(-1).to(torch.int64)
+    path_off = torch.zeros(4 * P + 1, dtype=torch.int64, device="cuda")
+    path_off[1:] = torch.cumsum(lens_o, 0)
+    mat_o = (4 * order[:, None] + torch.arange(4, device="cuda")[None, :]).reshape(-1)  # caller's index of run matrix k
+    shift = torch.repeat_interleave(path_off[:-1][mat_o] - run_off[:-1], lens.reshape(-1).to(torch.int64))
+    out = torch.empty_like(cells)
+    out[torch.arange(cells.shape[0], device="cuda") + shift] = cells
+    return {"scores": _unorder(order, scores), "seg": _unorder(order, seg), "path_off": path_off, "cells": out}
 
 
 def ef_block_features(chromas, mfccs, onsets, blocksize=20, mfccs_per_block=50, chromas_per_block=40):

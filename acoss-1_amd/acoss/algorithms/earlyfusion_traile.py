@@ -248,6 +248,65 @@ class EarlyFusion(CoverAlgorithm):
             self.times['raw'].append((time.time() - tic) / max(1, len(idxs)))
         return {key: sc[:, s].float() for s, key in enumerate(("mfccs", "ssms", "chromas", "early"))}
 
+    def _onsets(self, songs):
+        """{song: (beat onsets int64, chroma frame count)} read from the songs' feature files; the
+        block-feature cache holds neither."""
+        from ..features_io import load_many
+        songs = [int(i) for i in songs]
+        feats = load_many([self.filepaths[i] for i in songs], keys=(self.chroma_type, "madmom_features"))
+        out = {}
+        for i, f in zip(songs, feats):
+            mm = f.get("madmom_features")
+            if not isinstance(mm, dict) or "onsets" not in mm or self.chroma_type not in f:
+                raise ValueError("frames=True needs the beat onsets ('madmom_features'/'onsets') and the '%s' chroma "
+                                 "of song %d, and %s has none: the cached block features do not keep them"
+                                 % (self.chroma_type, i, self.filepaths[i]))
+            out[i] = (np.asarray(mm["onsets"], np.int64).reshape(-1), len(f[self.chroma_type]))
+        return out
+
+    def localize(self, idxs, frames=False):
+        """Where the four Smith-Waterman alignments of every (query, reference) pair of idxs lie
+        (acoss_earlyfusion_locate): a dict of host arrays 'scores' (P, 4) in the order mfccs, ssms,
+        chromas, early (similarity()'s values), 'cells' (P, 4, 4) = (r0, c0, r1, c1) in beat blocks
+        of the query (rows) and the reference (columns), 'query_blocks' and 'reference_blocks'
+        (P, 4, 2): the same as half-open block ranges [r0, r1 + 1) and [c0, c1 + 1). A matrix whose
+        score is 0 has cells (-1, -1, -1, -1) and ranges (-1, -1).
+        frames=True adds 'query_frames' and 'reference_frames' (P, 4, 2): half-open ranges of
+        `chroma_type` frames (engine.block_frames), from the beat onsets of the songs involved,
+        read from their feature files on demand; a ValueError names a song whose file has none.
+        Not collective: a rank localises the pairs it is given."""
+        idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
+        r = _lib.earlyfusion_locate(self._bank(), idxs, self.kappa, self.K)
+        cells = r["seg"].cpu().numpy()
+        out = {"scores": r["scores"].cpu().numpy(), "cells": cells}
+        none = cells[:, :, 0] < 0
+        for key, lo, hi in (("query_blocks", 0, 2), ("reference_blocks", 1, 3)):
+            b = np.stack([cells[:, :, lo], cells[:, :, hi] + 1], 2).astype(np.int64)
+            b[none] = -1
+            out[key] = b
+        if frames:
+            from ..engine import block_frames
+            on = self._onsets(np.unique(idxs))
+            for key, col, lo, hi in (("query_frames", 0, 0, 2), ("reference_frames", 1, 1, 3)):
+                fr = np.full((len(idxs), 4, 2), -1, np.int64)
+                for p, song in enumerate(idxs[:, col]):
+                    o, n = on[int(song)]
+                    fr[p] = block_frames(cells[p][:, [lo, hi]], o, self.blocksize, n)
+                out[key] = fr
+        return out
+
+    def align_path(self, idxs):
+        """The four alignments of every (query, reference) pair of idxs, cell by cell
+        (acoss_earlyfusion_path): a dict of host arrays 'scores' (P, 4) and 'cells' (P, 4, 4) as
+        localize, 'path_off' (4 P + 1,) int64 and 'path_cells' (total, 2) int32. The path of matrix s
+        (mfccs, ssms, chromas, early) of pair p is path_cells[path_off[4 p + s]:path_off[4 p + s + 1]]:
+        (query block, reference block) from cells[p, s, :2] to cells[p, s, 2:], each step (1, 1),
+        (2, 1) or (1, 2); empty where the score is 0. Not collective."""
+        idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
+        r = _lib.earlyfusion_path(self._bank(), idxs, self.kappa, self.K)
+        return {"scores": r["scores"].cpu().numpy(), "cells": r["seg"].cpu().numpy(),
+                "path_off": r["path_off"].cpu().numpy(), "path_cells": r["cells"].cpu().numpy()}
+
     def track_lengths(self):
         """Beat blocks per song: a pair costs nb_i * nb_j (three CSMs, four SW), so the row
         stripes balance that (acoss.distributed.stripe_bounds with m = tau = 0)."""

@@ -59,6 +59,27 @@ def subsequence_frames(idx, sslen, win, skip, n_frames):
     return r
 
 
+def block_frames(blocks, onsets, blocksize, n_frames):
+    """EarlyFusion beat blocks -> half-open ranges of chroma frames (pure numpy). blocks: (n, 2)
+    inclusive block ranges [b0, b1] of one track (or (n,) single blocks); onsets: the track's beat
+    onsets (frame indices), blocksize: beats per block, n_frames: its chroma frame count. Block b
+    covers the frames [o[b], min(o[b + blocksize], n_frames)) (acoss_ef_block_features), so a range
+    of blocks covers from the first block's start to the last block's end. Returns (n, 2) int64;
+    a block of -1 (no alignment) maps to (-1, -1), as an empty segment does in segment_frames."""
+    b = np.asarray(blocks, np.int64)
+    b = np.stack([b, b], 1) if b.ndim == 1 else b.reshape(-1, 2)
+    o = np.asarray(onsets, np.int64).reshape(-1)
+    ok = (b[:, 0] >= 0) & (b[:, 1] >= 0)
+    r = np.full((len(b), 2), -1, np.int64)
+    if ok.any():
+        if int(b[ok].max()) + blocksize >= len(o):
+            raise ValueError("block %d of a track with %d onsets at %d beats per block"
+                             % (int(b[ok].max()), len(o), blocksize))
+        r[ok, 0] = o[b[ok, 0]]
+        r[ok, 1] = np.minimum(o[b[ok, 1] + blocksize], int(n_frames))
+    return r
+
+
 class ChromaBank:
     """12-bin chroma of a whole corpus resident on the current GPU."""
 

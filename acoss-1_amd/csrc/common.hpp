@@ -115,6 +115,17 @@ __device__ inline double wave_max(double v) {
 // Value of lane `src` (wave-uniform) in every lane: v_readlane, no LDS.
 __device__ __forceinline__ int lane_bcast(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 
+// The n cells a backtrack (crp_dp.hip, sw_path.hip) left in out[], last to first, turned round by
+// the whole wave, and -1 after them up to path_cap.
+__device__ __forceinline__ void path_turn_and_pad(int2* out, int n, int path_cap, int lane) {
+  for (int t = lane; t < n / 2; t += 64) {
+    const int2 a = out[t], b = out[n - 1 - t];
+    out[t] = b;
+    out[n - 1 - t] = a;
+  }
+  for (int t = n + lane; t < path_cap; t += 64) out[t] = make_int2(-1, -1);
+}
+
 // XCD-aware block swizzle (speed only, never correctness): blocks are dealt round-robin over
 // the 8 XCDs, so linear ids b and b + 8 share an L2. This bijection on [0, nwg) makes runs of
 // consecutive LOGICAL ids share one XCD (MI355X_MICROARCH.md, workgroup dispatch / T1).

@@ -887,16 +887,6 @@ __global__ __launch_bounds__(64) void k_crp_dp_dir(const uint32_t* __restrict__ 
 // first; then the whole wave turns them round in place and fills the rest of the pair's path_cap
 // entries with -1. seg (unless NULL): the first and last cell, (-1, -1, -1, -1) for no path.
 // --------------------------------------------------------------------------------------
-// the n cells a backtrack left in out[], last to first, turned round by the whole wave, and -1 after them
-__device__ __forceinline__ void path_turn_and_pad(int2* out, int n, int path_cap, int lane) {
-  for (int t = lane; t < n / 2; t += 64) {
-    const int2 a = out[t], b = out[n - 1 - t];
-    out[t] = b;
-    out[n - 1 - t] = a;
-  }
-  for (int t = n + lane; t < path_cap; t += 64) out[t] = make_int2(-1, -1);
-}
-
 __global__ __launch_bounds__(64) void k_crp_backtrack(const uint8_t* __restrict__ plane, int64_t plane_stride, int ld,
                                                       const int2* __restrict__ dims,
                                                       const uint32_t* __restrict__ endkey, int path_cap,

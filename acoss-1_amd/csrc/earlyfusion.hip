@@ -18,21 +18,20 @@
 //   k_ef_kmin*    thread per (row|column, pair, matrix): mean of the K smallest (K <= 16;
 //                 k_ef_kmean, a wave-per-line select, beyond that)
 //   k_ef_wsum     elementwise: E = exp(-(((0 + W_m) + W_s) + W_c)) in float32, exp = canon_expf
-//   SW            launch_swb_batch (misc.hip) over the 4P bit planes
+//   SW            launch_swb_batch (misc.hip) over the 4P bit planes; for the locate and path
+//                 entries launch_swt_locate / launch_swt_path (sw_path.hip) instead
 // Tolerance vs the reference: the GEMMs' summation order (BLAS vs MFMA), the k-smallest means'
 // order (ascending here, np.partition's unspecified there) and exp (canon_expf vs numpy's); every
 // other step is the reference's float32 arithmetic. Against the canonical CPU oracle
 // (oracle/ef_oracle.cpp) all four scores are bit-identical.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
 #include "common.hpp"
+#include "sw_internal.hpp"
 
 namespace acoss {
-
-int launch_swb_batch(const uint16_t* W, int64_t wstride, int ldw, const int32_t* rows, const int32_t* cols, int n,
-                     int max_rows, int max_cols, void* bnd, double* out, hipStream_t s);
-size_t sw_bnd_bytes(int max_rows, int max_cols);
 
 namespace {
 
@@ -1166,21 +1165,29 @@ __global__ void k_ef_swmeta(EfPairs E, int P, int32_t* rows, int32_t* cols) {
   }
 }
 
-}  // namespace
-}  // namespace acoss
+// What the batch driver does with a chunk's 4P bit planes, its last stage.
+enum EfStage { EF_SCORE, EF_LOCATE, EF_PATH };
 
-using namespace acoss;
-
-extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
-                                 const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
-                                 int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma,
-                                 const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K, float mu,
-                                 double* scores_out, void* hip_stream) {
+// The one driver under acoss_earlyfusion, acoss_earlyfusion_locate and acoss_earlyfusion_path: every
+// stage up to the four bit planes of each pair is the same; `stage` picks what runs over them.
+// seg_out: int32[n_pairs][4][4] (EF_LOCATE; optional for EF_PATH); len_out int32[n_pairs][4] and
+// path_out int32[n_pairs][4][path_cap][2] (EF_PATH).
+int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float* ssm, const float* chroma,
+               const float* chroma_med, const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
+               int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs,
+               int64_t n_pairs, double kappa, int32_t K, float mu, double* scores_out, int32_t* seg_out,
+               int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
   clear_error();
   if (n_tracks <= 0 || n_pairs < 0 || max_blocks <= 0 || d_mfcc <= 0 || d_ssm <= 0 || d_chroma <= 0 ||
       d_chroma % 12 != 0 || K <= 0 || K >= max_blocks + 1 || kappa < 0.0 ||
-      (n_pairs > 0 && (!mfcc || !ssm || !chroma || !chroma_med || !block_off || !n_blocks || !pairs || !scores_out))) {
-    set_error("acoss_earlyfusion: bad arguments");
+      (n_pairs > 0 && (!mfcc || !ssm || !chroma || !chroma_med || !block_off || !n_blocks || !pairs || !scores_out)) ||
+      (n_pairs > 0 && ((stage == EF_LOCATE && !seg_out) || (stage == EF_PATH && (!len_out || !path_out))))) {
+    set_error("%s: bad arguments", entry);
+    return ACOSS_E_ARG;
+  }
+  if (stage == EF_PATH && path_cap < std::max(1, sw_path_bound(max_blocks, max_blocks))) {
+    set_error("%s: path_cap %d below max(1, max_blocks - 3) = %d: a path may have that many cells", entry, path_cap,
+              std::max(1, sw_path_bound(max_blocks, max_blocks)));
     return ACOSS_E_ARG;
   }
   if (n_pairs == 0) return ACOSS_OK;
@@ -1225,9 +1232,13 @@ extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const floa
 
   // chunk of pairs: 3 CSMs (E overwrites the first), 4 binary matrices, 6 mean vectors, SW scratch
   const size_t mat = (size_t)ld * ld;
-  const size_t sw_b = sw_bnd_bytes(ld, ld);
+  // band-boundary records of the scoring walk or of the tracing / direction DP; for the paths also
+  // the direction plane (about ld^2 / 4 bytes) and the end key of each of the four matrices
+  const size_t sw_b = stage == EF_SCORE ? sw_bnd_bytes(ld, ld) : align_up(swt_bnd_bytes(ld, ld), 32);
+  const size_t plane_b = stage == EF_PATH ? swt_plane_bytes(ld, ld) : 0;
   const int64_t wplane = (int64_t)((ld + 15) / 16) * ld;  // u16 words of one bit plane
-  const size_t per_pair = 3 * mat * 4 + 4 * (size_t)wplane * 2 + 6 * (size_t)ld * 4 + 4 * sw_b + 4 * (4 + 4) + 4;
+  const size_t per_pair = 3 * mat * 4 + 4 * (size_t)wplane * 2 + 6 * (size_t)ld * 4 + 4 * sw_b + 4 * (4 + 4) + 4 +
+                          4 * (plane_b + (stage == EF_PATH ? 4 : 0));
   size_t budget = (size_t)4 << 30;
   if (const char* e = getenv("ACOSS_EF_BYTES")) budget = strtoull(e, nullptr, 10);
   // chunks alternate between two streams with a scratch set each, so one chunk's MFMA CSMs overlap
@@ -1257,6 +1268,8 @@ extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const floa
     void* bnd;
     int32_t *m_rows, *m_cols;
     int* oti;
+    void* plane;       // EF_PATH only
+    uint32_t* endkey;
   } sets[2];
   for (int q = 0; q < nset; ++q) {
     sets[q].C = reinterpret_cast<float*>(carve(3 * mat * 4 * chunk));
@@ -1267,6 +1280,8 @@ extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const floa
     sets[q].m_rows = reinterpret_cast<int32_t*>(carve(4 * 4 * chunk));
     sets[q].m_cols = reinterpret_cast<int32_t*>(carve(4 * 4 * chunk));
     sets[q].oti = reinterpret_cast<int*>(carve(4 * chunk));
+    sets[q].plane = carve(4 * plane_b * chunk);
+    sets[q].endkey = reinterpret_cast<uint32_t*>(carve(stage == EF_PATH ? 4 * 4 * chunk : 0));
   }
   hipStream_t ss[2] = {s, s};
   if (nset == 2) {
@@ -1412,7 +1427,17 @@ extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const floa
     prof_begin(PH_SW, st);
     hipLaunchKernelGGL(k_ef_swmeta, dim3((P + 255) / 256), dim3(256), 0, st, E, P, m_rows, m_cols);
     ACOSS_LAUNCH_CHECK();
-    int rc = launch_swb_batch(Wb, wplane, ld, m_rows, m_cols, 4 * P, ld, ld, bnd, scores_out + 4 * p0, st);
+    int rc;
+    if (stage == EF_SCORE)
+      rc = launch_swb_batch(Wb, wplane, ld, m_rows, m_cols, 4 * P, ld, ld, bnd, scores_out + 4 * p0, st);
+    else if (stage == EF_LOCATE)
+      rc = launch_swt_locate(Wb, wplane, ld, m_rows, m_cols, 4 * P, ld, ld, bnd, scores_out + 4 * p0, seg_out + 16 * p0,
+                             st);
+    else
+      rc = launch_swt_path(Wb, wplane, ld, m_rows, m_cols, 4 * P, ld, ld, bnd, sets[ci & (nset - 1)].plane,
+                           sets[ci & (nset - 1)].endkey, scores_out + 4 * p0, path_cap,
+                           seg_out ? seg_out + 16 * p0 : nullptr, len_out + 4 * p0,
+                           path_out + 8 * (size_t)path_cap * (size_t)p0, st);
     if (rc) return rc;
     prof_end(PH_SW, st);
   }
@@ -1422,4 +1447,40 @@ extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const floa
     ACOSS_HIP_CHECK(hipStreamWaitEvent(s, e1, 0));
   }
   return ACOSS_OK;
+}
+
+}  // namespace
+}  // namespace acoss
+
+using namespace acoss;
+
+extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                                 const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
+                                 int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma,
+                                 const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K, float mu,
+                                 double* scores_out, void* hip_stream) {
+  return ef_batches(EF_SCORE, "acoss_earlyfusion", mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks,
+                    max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, scores_out, nullptr, 0, nullptr,
+                    nullptr, hip_stream);
+}
+
+extern "C" int acoss_earlyfusion_locate(const float* mfcc, const float* ssm, const float* chroma,
+                                        const float* chroma_med, const int64_t* block_off, const int32_t* n_blocks,
+                                        int32_t n_tracks, int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm,
+                                        int32_t d_chroma, const int32_t* pairs, int64_t n_pairs, double kappa,
+                                        int32_t K, float mu, double* scores_out, int32_t* seg_out, void* hip_stream) {
+  return ef_batches(EF_LOCATE, "acoss_earlyfusion_locate", mfcc, ssm, chroma, chroma_med, block_off, n_blocks,
+                    n_tracks, max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, scores_out, seg_out,
+                    0, nullptr, nullptr, hip_stream);
+}
+
+extern "C" int acoss_earlyfusion_path(const float* mfcc, const float* ssm, const float* chroma,
+                                      const float* chroma_med, const int64_t* block_off, const int32_t* n_blocks,
+                                      int32_t n_tracks, int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm,
+                                      int32_t d_chroma, const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K,
+                                      float mu, double* scores_out, int32_t* seg_out, int32_t path_cap,
+                                      int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  return ef_batches(EF_PATH, "acoss_earlyfusion_path", mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks,
+                    max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, scores_out, seg_out, path_cap,
+                    len_out, path_out, hip_stream);
 }

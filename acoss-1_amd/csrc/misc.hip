@@ -5,9 +5,12 @@
 //   csm_to_binary        cross_recurrence.py:136-161
 //   getWCSM              acoss/algorithms/utils/similarity_fusion.py:38-54
 //   smith_waterman_constrained   acoss/algorithms/utils/alignment_tools.py:7-46
+//     and where its alignment lies (acoss_sw_locate, acoss_sw_path; the kernels are in sw_path.hip)
+#include <algorithm>
 #include <cstdlib>
 
 #include "common.hpp"
+#include "sw_internal.hpp"
 
 namespace acoss {
 
@@ -648,4 +651,80 @@ extern "C" int acoss_sw_constrained(const uint8_t* mats, const int64_t* off, con
     return ACOSS_E_NONBINARY;
   }
   return ACOSS_OK;
+}
+
+namespace {
+
+// acoss_sw_locate (path = false) and acoss_sw_path: acoss_sw_constrained's packing, then the
+// tracing DP, or the direction DP and the walk back (sw_path.hip).
+int sw_where(const char* entry, bool path, const uint8_t* mats, const int64_t* off, const int32_t* rows,
+             const int32_t* cols, int32_t n_mats, int32_t max_rows, int32_t max_cols, double* score_out,
+             int32_t* seg_out, int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  clear_error();
+  if (n_mats < 0 || max_rows < 0 || max_cols < 0 ||
+      (n_mats > 0 && (!mats || !off || !rows || !cols || (path ? !len_out || !path_out : !seg_out)))) {
+    set_error("%s: bad arguments", entry);
+    return ACOSS_E_ARG;
+  }
+  if (max_rows > kSwCellMax || max_cols > kSwCellMax) {
+    set_error("%s: %d x %d: a cell is packed into 16 + 16 bits, at most %d rows and columns", entry, max_rows,
+              max_cols, kSwCellMax);
+    return ACOSS_E_SHAPE;
+  }
+  const int bound = std::max(1, sw_path_bound(max_rows, max_cols));
+  if (path && path_cap < bound) {
+    set_error("%s: path_cap %d below max(1, min(max_rows, max_cols) - 3) = %d: a path may have that many cells", entry,
+              path_cap, bound);
+    return ACOSS_E_ARG;
+  }
+  if (n_mats == 0) return ACOSS_OK;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const int G = (max_rows + 15) / 16;
+  const int ldw = (int)align_up((size_t)max_cols, 4);
+  const int64_t wstride = (int64_t)G * ldw;
+  const size_t bnd_b = align_up(swt_bnd_bytes(max_rows, max_cols) * n_mats, 256);
+  const size_t w_b = align_up((size_t)wstride * 2 * n_mats, 256);
+  const size_t plane_b = path ? swt_plane_bytes(max_rows, max_cols) * n_mats : 0;
+  char* ws = static_cast<char*>(workspace(26, 256 + bnd_b + w_b + plane_b + 4 * (size_t)n_mats));
+  if (!ws) return ACOSS_E_HIP;
+  int* d_err = reinterpret_cast<int*>(ws);
+  void* bnd = ws + 256;
+  uint16_t* W = reinterpret_cast<uint16_t*>(ws + 256 + bnd_b);
+  void* plane = ws + 256 + bnd_b + w_b;
+  uint32_t* endkey = reinterpret_cast<uint32_t*>(ws + 256 + bnd_b + w_b + plane_b);
+  ACOSS_HIP_CHECK(hipMemsetAsync(d_err, 0, 4, s));
+  if (G > 0 && max_cols > 0) {
+    hipLaunchKernelGGL(k_sw_pack, dim3(n_mats, G, (max_cols + 255) / 256), dim3(256), 0, s, mats, off, rows, cols, W,
+                       wstride, ldw, d_err);
+    ACOSS_LAUNCH_CHECK();
+  }
+  const int rc = path ? launch_swt_path(W, wstride, ldw, rows, cols, n_mats, max_rows, max_cols, bnd, plane, endkey,
+                                        score_out, path_cap, seg_out, len_out, path_out, s)
+                      : launch_swt_locate(W, wstride, ldw, rows, cols, n_mats, max_rows, max_cols, bnd, score_out,
+                                          seg_out, s);
+  if (rc) return rc;
+  int h_err = 0;
+  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  if (h_err) {
+    set_error("smith_waterman_constrained: Non-binary elements found in input");
+    return ACOSS_E_NONBINARY;
+  }
+  return ACOSS_OK;
+}
+
+}  // namespace
+
+extern "C" int acoss_sw_locate(const uint8_t* mats, const int64_t* off, const int32_t* rows, const int32_t* cols,
+                               int32_t n_mats, int32_t max_rows, int32_t max_cols, double* score_out,
+                               int32_t* seg_out, void* hip_stream) {
+  return sw_where("acoss_sw_locate", false, mats, off, rows, cols, n_mats, max_rows, max_cols, score_out, seg_out, 0,
+                  nullptr, nullptr, hip_stream);
+}
+
+extern "C" int acoss_sw_path(const uint8_t* mats, const int64_t* off, const int32_t* rows, const int32_t* cols,
+                             int32_t n_mats, int32_t max_rows, int32_t max_cols, double* score_out, int32_t* seg_out,
+                             int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  return sw_where("acoss_sw_path", true, mats, off, rows, cols, n_mats, max_rows, max_cols, score_out, seg_out,
+                  path_cap, len_out, path_out, hip_stream);
 }

@@ -190,6 +190,49 @@ int acoss_path_crp_dmax(const uint8_t* crp, int32_t M, int32_t N, float gamma_op
 int acoss_sw_constrained(const uint8_t* mats, const int64_t* off, const int32_t* rows, const int32_t* cols,
                          int32_t n_mats, int32_t max_rows, int32_t max_cols, double* score_out, void* hip_stream);
 
+/* WHERE the constrained Smith-Waterman alignment lies: acoss_sw_constrained with, per matrix, the
+ * first and last cell of the alignment behind the score (acoss_sw_locate) or every cell of it
+ * (acoss_sw_path). The reference fills a whole score matrix and returns only its maximum; here the
+ * tracing DP carries the cell where each path began beside every score and writes no matrix, and
+ * the direction DP leaves a 2-bit predecessor code per cell in a workspace plane of about M N / 4
+ * bytes per matrix that a second kernel walks back (sw_path.hip k_swt, k_sw_backtrack). Inputs as
+ * acoss_sw_constrained. score_out: double[n_mats], may be NULL, acoss_sw_constrained's bit for bit.
+ * seg_out: int32[4 n_mats] = (r0, c0, r1, c1) per matrix (may be NULL for acoss_sw_path). len_out:
+ * int32[n_mats]; path_out: int32[n_mats][path_cap][2], the path's cells (r, c) first to last, the
+ * rest -1.
+ *
+ * The definition. B is the binary M x N matrix, S the score matrix of oracle/crp_oracle.cpp
+ * or_sw_constrained, all arithmetic float64. Cells are named in B's own coordinates: the
+ * reference's score_matrix[i][j] is the cell X = (i - 1, j - 1) here.
+ *   scored cells: 2 <= r <= M - 2 and 2 <= c <= N - 2, the reference's loop bounds; every other
+ *     cell holds 0.
+ *   m(X) = +1 if B[X] else -1; pen(P) = 0 if B[P] else -0.7.
+ *   predecessors of X = (r, c), in this fixed order:
+ *     a: P = (r-1, c-1)     b: P = (r-2, c-1)     c: P = (r-1, c-2)
+ *   each with the value x_k = (S[P_k] + m(X)) + pen(P_k), in exactly that association.
+ *   score of a cell: S[X] = max(x_a, x_b, x_c, 0).
+ *   chosen predecessor: the FIRST of a, b, c attaining the maximum (a strictly greater value
+ *     replaces, an equal one does not). A cell with S[X] == 0 has none; a cell whose chosen
+ *     predecessor has S[P] == 0 begins a path, and P is not on the path.
+ *   score = max S; end cell: the first cell in row-major order holding it (the reference's > keeps
+ *     the first).
+ *   path: from the end cell follow chosen predecessors while S[P] > 0; reported origin to end.
+ *     Strictly increasing in r and c, steps (1, 1), (2, 1) and (1, 2); every cell lies in
+ *     [2, M-2] x [2, N-2] and has S > 0; misses may lie on it (the gaps the -1 paid for); at most
+ *     max(0, min(M, N) - 3) cells.
+ *   segment: (r0, c0, r1, c1) = (origin, end); (-1, -1, -1, -1) and an empty path where the score
+ *     is 0, always so for M < 4 or N < 4.
+ *   check of a path: re-accumulating x along it, from 0 at the origin's chosen predecessor,
+ *     reproduces the score bit for bit.
+ * path_cap below max(1, min(max_rows, max_cols) - 3) returns ACOSS_E_ARG, the message naming the
+ * bound; a byte other than 0 / 1 ACOSS_E_NONBINARY; max_rows or max_cols above 65,535
+ * ACOSS_E_SHAPE (a cell is packed into 16 + 16 bits). */
+int acoss_sw_locate(const uint8_t* mats, const int64_t* off, const int32_t* rows, const int32_t* cols, int32_t n_mats,
+                    int32_t max_rows, int32_t max_cols, double* score_out, int32_t* seg_out, void* hip_stream);
+int acoss_sw_path(const uint8_t* mats, const int64_t* off, const int32_t* rows, const int32_t* cols, int32_t n_mats,
+                  int32_t max_rows, int32_t max_cols, double* score_out, int32_t* seg_out, int32_t path_cap,
+                  int32_t* len_out, int32_t* path_out, void* hip_stream);
+
 /* Cross-similarity matrices (A5/A6/A2): acoss get_csm / get_csm_cosine
  * (cross_recurrence.py:30-73), optionally after get_csm_blocked_oti's query rotation
  * (:105-134): with oti_shift >= 0 every 12-bin block of each X row is rolled by oti_shift
@@ -384,6 +427,26 @@ int acoss_earlyfusion(const float* mfcc, const float* ssm, const float* chroma, 
                       const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
                       int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
                       double kappa, int32_t K, float mu, double* scores_out, void* hip_stream);
+
+/* acoss_earlyfusion with WHERE each of the four alignments lies: the same stages up to the four
+ * binary matrices of every pair (rows: the query's blocks, columns: the reference's), then
+ * acoss_sw_locate's or acoss_sw_path's kernels over them (the definition is there). Arguments as
+ * acoss_earlyfusion; scores_out: double[4 n_pairs], acoss_earlyfusion's bit for bit. seg_out:
+ * int32[n_pairs][4][4] = (r0, c0, r1, c1) of matrix s (mfccs, ssms, chromas, early) of pair p, in
+ * blocks (may be NULL for the path entry); len_out: int32[n_pairs][4]; path_out:
+ * int32[n_pairs][4][path_cap][2], padded with -1. path_cap below max(1, max_blocks - 3) returns
+ * ACOSS_E_ARG, the message naming the bound. The direction planes (about ld^2 bytes per pair for
+ * the four matrices) enter the per-pair chunk size of the path entry only. */
+int acoss_earlyfusion_locate(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                             const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                             int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
+                             double kappa, int32_t K, float mu, double* scores_out, int32_t* seg_out,
+                             void* hip_stream);
+int acoss_earlyfusion_path(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                           const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                           int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
+                           double kappa, int32_t K, float mu, double* scores_out, int32_t* seg_out, int32_t path_cap,
+                           int32_t* len_out, int32_t* path_out, void* hip_stream);
 
 /* EarlyFusion beat-synchronous block features of a batch of tracks (replaces
  * EarlyFusion.load_features' block loops, acoss/algorithms/earlyfusion_traile.py:67-154, and its
