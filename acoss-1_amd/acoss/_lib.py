@@ -81,6 +81,8 @@ SIGNATURES = {
                                  ctypes.c_double, _i32, _f32, _vp, _vp, _vp],
     "acoss_earlyfusion_path": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, ctypes.c_double,
                                _i32, _f32, _vp, _vp, _i32, _vp, _vp, _vp],
+    "acoss_earlyfusion_snf": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, ctypes.c_double,
+                              _i32, _f32, _i32, ctypes.c_double, _vp, _vp, _i64, _vp, _vp],
     "acoss_ef_block_features": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                 _vp, _vp],
     "acoss_ftm2d_shingles": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, ctypes.c_double, ctypes.c_double, _vp, _vp],
@@ -914,6 +916,88 @@ def earlyfusion(bank, pairs, kappa=0.1, K=10, mu=0.5):
     if order is not None:
         out[order] = dst
     return out
+
+
+EF_SNF_MAX_K = 64         # neighbours per row of acoss_earlyfusion_snf
+EF_SNF_MAX_BLOCKS = 512   # blocks per track
+EF_SNF_LDS_N = 101        # pairs of up to this many blocks in all fuse inside one workgroup's LDS
+
+
+def ef_snf_pair_ok(M, N, K):
+    """Whether the reference can fuse a pair of M and N blocks at all (host only, numpy): getW's
+    np.partition(DSym, k + 1) needs 1 <= k1 <= M - 2 and 1 <= k2 <= N - 2 (k = 0 divides by zero),
+    getS's argpartition K < M + N; k1 = int(K M / (M + N)), k2 = K - k1 (similarity_fusion.py:93-94)."""
+    M = np.asarray(M, np.int64)
+    N = np.asarray(N, np.int64)
+    k1 = (K * M.astype(np.float64) / np.maximum(M + N, 1)).astype(np.int64)
+    k2 = K - k1
+    return (M + N > K) & (k1 >= 1) & (k1 <= M - 2) & (k2 >= 1) & (k2 <= N - 2)
+
+
+def ef_snf_cross_offsets(nb, pairs):
+    """Where each pair's M x N cross matrix starts in the ragged output of earlyfusion_snf (host
+    only): int64 (P + 1,)."""
+    nb = np.asarray(nb, np.int64).reshape(-1)
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if len(pairs) and (int(pairs.min()) < 0 or int(pairs.max()) >= len(nb)):
+        raise ValueError("pair indices must lie in [0, %d)" % len(nb))
+    off = np.zeros(len(pairs) + 1, np.int64)
+    np.cumsum(nb[pairs[:, 0]] * nb[pairs[:, 1]], out=off[1:])
+    return off
+
+
+def ef_snf_check_args(kappa, K, niters, reg_diag, max_blocks=None):
+    """The argument errors of earlyfusion_snf that need no GPU (ValueError)."""
+    if int(niters) != niters or niters < 0:
+        raise ValueError("niters must be a non-negative integer, got %r" % (niters,))
+    if not reg_diag >= 0:
+        raise ValueError("reg_diag must be >= 0, got %r" % (reg_diag,))
+    if int(K) != K or not 1 <= K <= EF_SNF_MAX_K:
+        raise ValueError("K must be an integer in [1, %d], got %r" % (EF_SNF_MAX_K, K))
+    if not kappa >= 0:
+        raise ValueError("kappa must be >= 0, got %r" % (kappa,))
+    if max_blocks is not None and max_blocks > EF_SNF_MAX_BLOCKS:
+        raise ValueError("early SNF takes tracks of at most %d blocks, got %d" % (EF_SNF_MAX_BLOCKS, max_blocks))
+
+
+def earlyfusion_snf(bank, pairs, kappa, K, niters, reg_diag=1.0, want_cross=False, mu=0.5):
+    """The per-pair similarity network fusion score of EarlyFusion (acoss_earlyfusion_snf; the
+    definition is in include/acoss_hip.h). bank as earlyfusion() takes it. Returns a dict of device
+    tensors: "score" f64 (P,), NaN for a pair the reference cannot fuse (ef_snf_pair_ok); with
+    want_cross also "cross_off" i64 (P + 1,) and "cross" f64 (cross_off[-1],), pair p's M x N
+    cross block of the fused matrix, row-major (both None otherwise). A kappa whose neighbour count
+    reaches a reference's block count raises the reference's ValueError, as earlyfusion() does."""
+    ef_snf_check_args(kappa, K, niters, reg_diag, bank.get("max_blocks"))
+    torch = _torch()
+    lib = load_library()
+    T = int(bank["nb"].shape[0])
+    pairs, host = _pairs_dev(pairs, T)
+    P = pairs.shape[0]
+    score = torch.empty(P, dtype=torch.float64, device="cuda")
+    nb_host = np.asarray(bank["nb_host"]) if "nb_host" in bank else bank["nb"].cpu().numpy()
+    if host is None:
+        host = pairs.cpu().numpy()
+    if P and kappa != 0:  # csm_to_binary's argpartition(D, nn, 1) needs nn < ncols (cross_recurrence.py:150-156)
+        lo = int(nb_host[host[:, 1]].min())  # n - round(kappa n) never decreases with n: the smallest decides
+        nn = int(np.round(kappa * lo)) if kappa < 1 else int(kappa)
+        if nn >= lo:
+            raise ValueError("kth(=%d) out of bounds (%d)" % (nn, lo))
+    off_d = cross = None
+    total = 0
+    if want_cross:
+        off = ef_snf_cross_offsets(nb_host, host)
+        total = int(off[-1])
+        off_d = _dev(off, torch.int64)
+        cross = torch.empty(total, dtype=torch.float64, device="cuda")
+    if P:
+        rc = lib.acoss_earlyfusion_snf(_ptr(bank["mfccs"]), _ptr(bank["ssms"]), _ptr(bank["chromas"]),
+                                       _ptr(bank["chroma_med"]), _ptr(bank["off"]), _ptr(bank["nb"]), T,
+                                       int(bank["max_blocks"]), int(bank["mfccs"].shape[1]),
+                                       int(bank["ssms"].shape[1]), int(bank["chromas"].shape[1]), _ptr(pairs), int(P),
+                                       float(kappa), int(K), float(mu), int(niters), float(reg_diag), _ptr(score),
+                                       _ptr(off_d), total, _ptr(cross) if total else None, _stream())
+        _check(rc, "acoss_earlyfusion_snf")
+    return {"score": score, "cross_off": off_d, "cross": cross}
 
 
 def _ef_args(bank, pairs, kappa, K, mu):

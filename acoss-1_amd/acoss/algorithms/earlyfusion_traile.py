@@ -58,7 +58,7 @@ class EarlyFusion(CoverAlgorithm):
 
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='Covers80', blocksize=20,
                  mfccs_per_block=50, ssm_res=50, chromas_per_block=40, kappa=0.1, K=10, niters=5, log_times=False,
-                 cachedir="cache"):
+                 cachedir="cache", early_snf=False):
         self.chroma_type = chroma_type
         self.blocksize = blocksize
         self.mfccs_per_block = mfccs_per_block
@@ -66,6 +66,11 @@ class EarlyFusion(CoverAlgorithm):
         self.kappa = kappa
         self.K = K
         self.niters = niters
+        # early_snf=True adds the per-pair similarity network fusion score (acoss_earlyfusion_snf:
+        # niters rounds of cross-diffusion of the three (M+N) x (M+N) parent matrices of a pair)
+        self.early_snf = bool(early_snf)
+        if self.early_snf:
+            _lib.ef_snf_check_args(kappa, K, niters, 1.0)
         self.all_block_feats = {}
         self.log_times = log_times
         if log_times:
@@ -73,8 +78,9 @@ class EarlyFusion(CoverAlgorithm):
         self._dev = {}
         self._pending = []  # background cache writes (flush_cache)
         CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name="EarlyFusionTraile", datapath=datapath,
-                                shortname=shortname, similarity_types=["mfccs", "ssms", "chromas", "early"],
-                                cachedir=cachedir)
+                                shortname=shortname,
+                                similarity_types=["mfccs", "ssms", "chromas", "early"] +
+                                (["early_snf"] if self.early_snf else []), cachedir=cachedir)
 
     def get_cacheprefix(self):
         return "%s/%s_%s_%s" % (self.cachedir, self.name, self.shortname, self.chroma_type)
@@ -236,6 +242,9 @@ class EarlyFusion(CoverAlgorithm):
             self.times['raw'].append((time.time() - tic) / len(idxs))
         for s, key in enumerate(("mfccs", "ssms", "chromas", "early")):
             self.Ds[key][idxs[:, 0], idxs[:, 1]] = scores[:, s]
+        if self.early_snf:
+            snf = _lib.earlyfusion_snf(self._bank(), idxs.astype(np.int32), self.kappa, self.K, self.niters)
+            self.Ds["early_snf"][idxs[:, 0], idxs[:, 1]] = snf["score"].cpu().numpy()
 
     def _device_scores(self, idxs):
         """The four scores of every pair as float32 device tensors (the memmap's dtype), from one
@@ -246,7 +255,29 @@ class EarlyFusion(CoverAlgorithm):
         sc = _lib.earlyfusion(self._bank(), idxs.astype(np.int32), self.kappa, self.K)
         if self.log_times:
             self.times['raw'].append((time.time() - tic) / max(1, len(idxs)))
-        return {key: sc[:, s].float() for s, key in enumerate(("mfccs", "ssms", "chromas", "early"))}
+        out = {key: sc[:, s].float() for s, key in enumerate(("mfccs", "ssms", "chromas", "early"))}
+        if self.early_snf:
+            out["early_snf"] = _lib.earlyfusion_snf(self._bank(), idxs.astype(np.int32), self.kappa, self.K,
+                                                    self.niters)["score"].float()
+        return out
+
+    def pair_fusion(self, i, j):
+        """(cross, binary) of pair (i, j): the M x N cross block F[:M, M:] + F[M:, :M].T of the pair's
+        fused matrix (host float64; NaN where the reference cannot fuse the pair) and the binary
+        matrix the early_snf score aligns (host uint8: round(kappa N) ones per row at the largest
+        values, ties to the lowest column). Beside pair_matrices, for the plots of the reference's
+        do_plot branch (:184-196)."""
+        r = _lib.earlyfusion_snf(self._bank(), np.array([[i, j]], np.int32), self.kappa, self.K, self.niters,
+                                 want_cross=True)
+        nb = self._bank()["nb_host"]
+        cross = r["cross"].cpu().numpy().reshape(int(nb[i]), int(nb[j]))
+        binary = np.zeros(cross.shape, np.uint8)
+        if self.kappa == 0:
+            binary[:] = 1
+        elif not np.isnan(cross).any():
+            idx = np.argsort(-cross, axis=1, kind="stable")[:, :nneighbs(self.kappa, cross.shape[1])]
+            np.put_along_axis(binary, idx, 1, 1)
+        return cross, binary
 
     def _onsets(self, songs):
         """{song: (beat onsets int64, chroma frame count)} read from the songs' feature files; the

@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "ef_internal.hpp"
 #include "sw_internal.hpp"
 
 namespace acoss {
@@ -80,19 +81,6 @@ __global__ void k_ef_oti(const float* __restrict__ med, const int32_t* __restric
     }
   }
   oti[p] = best;
-}
-
-struct EfPairs {
-  const int32_t* pairs;
-  const int64_t* off;  // block offsets per track
-  const int32_t* nb;   // blocks per track
-};
-
-__device__ __forceinline__ void pair_dims(const EfPairs& E, int p, int* a, int* b, int* M, int* N) {
-  *a = E.pairs[2 * p];
-  *b = E.pairs[2 * p + 1];
-  *M = E.nb[*a];
-  *N = E.nb[*b];
 }
 
 template <int KIND>  // 0 euclid, 1 cosine (pre-normalised rows, query blocks rolled by oti)
@@ -1165,6 +1153,111 @@ __global__ void k_ef_swmeta(EfPairs E, int P, int32_t* rows, int32_t* cols) {
   }
 }
 
+}  // namespace
+
+int ef_prepare(const EfBank& B, hipStream_t s, EfPrep* out) {
+  // per-track scratch: squared norms of the MFCC and SSM blocks, normalised chroma blocks; the
+  // caller's block_off / n_blocks give the total row count through the last track
+  int64_t h_off = 0;
+  int32_t h_nb = 0;
+  ACOSS_HIP_CHECK(hipMemcpy(&h_off, B.block_off + (B.n_tracks - 1), 8, hipMemcpyDeviceToHost));
+  ACOSS_HIP_CHECK(hipMemcpy(&h_nb, B.n_blocks + (B.n_tracks - 1), 4, hipMemcpyDeviceToHost));
+  const int64_t nrows = h_off + h_nb;
+  const size_t tr_bytes = align_up((size_t)nrows * 4, 256) * 2 + align_up((size_t)nrows * B.d_chroma * 4, 256);
+  char* tws = static_cast<char*>(workspace(10, tr_bytes));
+  if (!tws) return ACOSS_E_HIP;
+  float* sq_m = reinterpret_cast<float*>(tws);
+  float* sq_s = reinterpret_cast<float*>(tws + align_up((size_t)nrows * 4, 256));
+  float* chn = reinterpret_cast<float*>(tws + 2 * align_up((size_t)nrows * 4, 256));
+  prof_begin(PH_CSM, s);
+  const unsigned rb = (unsigned)((nrows + 3) / 4);
+  hipLaunchKernelGGL(k_ef_rows, dim3(rb), dim3(256), 0, s, B.mfcc, nrows, B.d_mfcc, 0, nullptr, sq_m);
+  ACOSS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ef_rows, dim3(rb), dim3(256), 0, s, B.ssm, nrows, B.d_ssm, 0, nullptr, sq_s);
+  ACOSS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ef_rows, dim3(rb), dim3(256), 0, s, B.chroma, nrows, B.d_chroma, 1, chn, nullptr);
+  ACOSS_LAUNCH_CHECK();
+  static const bool wave_tiles = getenv("ACOSS_EF_LDS_CSM") == nullptr;
+  const float* ssm_p = nullptr;  // SSM bank with rows padded to a multiple of 4 (k_ef_csm_w)
+  if (wave_tiles && B.d_ssm % 4 != 0) {
+    const int ldp = (int)align_up((size_t)B.d_ssm, 4);
+    float* pb = static_cast<float*>(workspace(15, (size_t)nrows * ldp * 4));
+    if (!pb) return ACOSS_E_HIP;
+    hipLaunchKernelGGL(k_ef_pad_rows, dim3(rb), dim3(256), 0, s, B.ssm, nrows, B.d_ssm, ldp, pb);
+    ACOSS_LAUNCH_CHECK();
+    ssm_p = pb;
+  }
+  prof_end(PH_CSM, s);
+  *out = EfPrep{sq_m, sq_s, chn, ssm_p, nrows};
+  return ACOSS_OK;
+}
+
+int ef_launch_csms(const EfBank& B, const EfPrep& R, const int32_t* pairs, int P, int ld, int* oti, bool self_pairs,
+                   float* C, int64_t mstride, hipStream_t st) {
+  static const bool wave_tiles = getenv("ACOSS_EF_LDS_CSM") == nullptr;
+  const EfPairs E{pairs, B.block_off, B.n_blocks};
+  const int tiles = (ld + kT - 1) / kT;  // LDS kernel tiles
+  // wave-tile CSMs: 32 x 32 tiles when every track has at most 64 blocks (Da-TACOS beat blocks:
+  // 14..47, a 64 x 64 tile there is mostly padding; profiles/r05/ef_short), 64 x 64 otherwise
+  const int wtile = ld <= 64 ? 32 : 64;
+  const int wtiles = (ld + wtile - 1) / wtile;
+  auto kw_euclid = wtile == 32 ? k_ef_csm_w<0, 32> : k_ef_csm_w<0, 64>;
+  auto kw_cosine = wtile == 32 ? k_ef_csm_w<1, 32> : k_ef_csm_w<1, 64>;
+  // short tracks: the cosine CSM with several consecutive pairs per wave sharing their query rows
+  // (k_ef_csm_w4); ACOSS_EF_W4=0 keeps one pair per wave
+  static const bool w4 = !(getenv("ACOSS_EF_W4") && getenv("ACOSS_EF_W4")[0] == '0');
+  // ... and the euclid CSMs with the reference columns of a query's run packed (k_ef_csm_pack):
+  // 32 x 64 tiles (pack_nb = 2) for every track up to 128 blocks; ACOSS_EF_PACK=1 takes 32 x 32
+  // tiles, 0 a tile per pair (Da-TACOS shapes, profiles/r06/ef_pack/README.txt: 14..47 blocks
+  // 4.85M -> 5.72M pairs/s, 30..80 blocks 1.12M -> 1.62M; 32 x 32 tiles 5.68M / 1.59M)
+  static const char* pack_env = getenv("ACOSS_EF_PACK");
+  const int pack_nb = ld > 128 || (pack_env && pack_env[0] == '0') ? 0 : pack_env && pack_env[0] == '1' ? 1 : 2;
+  prof_begin(PH_CSM, st);
+  if (self_pairs)
+    ACOSS_HIP_CHECK(hipMemsetAsync(oti, 0, (size_t)P * 4, st));
+  else
+    hipLaunchKernelGGL(k_ef_oti, dim3((P + 255) / 256), dim3(256), 0, st, B.chroma_med, pairs, P, oti);
+  ACOSS_LAUNCH_CHECK();
+  {
+    const int n_tiles = tiles * tiles * P, n_wtiles = wtiles * wtiles * P;
+    auto euclid = [&](const float* bank, int d, const float* sq, float* dst) -> int {
+      if (wave_tiles && d % 4 != 0 && bank == B.ssm && R.ssm_p) {
+        bank = R.ssm_p;  // the row-padded copy made by ef_prepare
+        d = (int)align_up((size_t)d, 4);
+      }
+      if (wave_tiles && d % 4 == 0 && pack_nb) {
+        const int tw = 32 * pack_nb;
+        const int units = (P + kEfPack - 1) / kEfPack * ((ld + 31) / 32) * (kEfPack * ((ld + tw - 1) / tw));
+        hipLaunchKernelGGL(pack_nb == 1 ? k_ef_csm_pack<1> : k_ef_csm_pack<2>, dim3((unsigned)((units + 3) / 4)),
+                           dim3(256), 0, st, bank, d, sq, E, ld, P, units, dst);
+      } else if (wave_tiles && d % 4 == 0)
+        hipLaunchKernelGGL(kw_euclid, dim3((unsigned)((n_wtiles + 3) / 4)), dim3(256), 0, st, bank, d, sq, E, oti, ld,
+                           n_wtiles, dst);
+      else
+        hipLaunchKernelGGL(k_ef_csm<0>, dim3((unsigned)n_tiles), dim3(256), 0, st, bank, d, sq, E, oti, ld, dst);
+      ACOSS_LAUNCH_CHECK();
+      return ACOSS_OK;
+    };
+    if (euclid(B.mfcc, B.d_mfcc, R.sq_m, C) != ACOSS_OK || euclid(B.ssm, B.d_ssm, R.sq_s, C + mstride) != ACOSS_OK)
+      return ACOSS_E_HIP;
+  }
+  if (wave_tiles && B.d_chroma % 24 == 0 && w4 && wtile == 32) {
+    const int units = (P + kEfPPc - 1) / kEfPPc * wtiles * wtiles;
+    hipLaunchKernelGGL((k_ef_csm_w4<1, kEfPPc>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, st, R.chn,
+                       B.d_chroma, nullptr, E, oti, ld, P, units, C + 2 * mstride);
+  } else if (wave_tiles && B.d_chroma % 24 == 0)
+    hipLaunchKernelGGL(kw_cosine, dim3((unsigned)((wtiles * wtiles * P + 3) / 4)), dim3(256), 0, st, R.chn, B.d_chroma,
+                       nullptr, E, oti, ld, wtiles * wtiles * P, C + 2 * mstride);
+  else
+    hipLaunchKernelGGL(k_ef_csm<1>, dim3((unsigned)(tiles * tiles * P)), dim3(256), 0, st, R.chn, B.d_chroma, nullptr, E,
+                       oti, ld, C + 2 * mstride);
+  ACOSS_LAUNCH_CHECK();
+  prof_end(PH_CSM, st);
+  return ACOSS_OK;
+}
+
+namespace {
+
 // What the batch driver does with a chunk's 4P bit planes, its last stage.
 enum EfStage { EF_SCORE, EF_LOCATE, EF_PATH };
 
@@ -1197,38 +1290,9 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
     set_error("acoss_earlyfusion: more than 16384 blocks in a track");
     return ACOSS_E_ARG;
   }
-  // per-track scratch: squared norms of the MFCC and SSM blocks, normalised chroma blocks; the
-  // caller's block_off / n_blocks give the total row count through the last track
-  int64_t h_off = 0;
-  int32_t h_nb = 0;
-  ACOSS_HIP_CHECK(hipMemcpy(&h_off, block_off + (n_tracks - 1), 8, hipMemcpyDeviceToHost));
-  ACOSS_HIP_CHECK(hipMemcpy(&h_nb, n_blocks + (n_tracks - 1), 4, hipMemcpyDeviceToHost));
-  const int64_t nrows = h_off + h_nb;
-  const size_t tr_bytes = align_up((size_t)nrows * 4, 256) * 2 + align_up((size_t)nrows * d_chroma * 4, 256);
-  char* tws = static_cast<char*>(workspace(10, tr_bytes));
-  if (!tws) return ACOSS_E_HIP;
-  float* sq_m = reinterpret_cast<float*>(tws);
-  float* sq_s = reinterpret_cast<float*>(tws + align_up((size_t)nrows * 4, 256));
-  float* chn = reinterpret_cast<float*>(tws + 2 * align_up((size_t)nrows * 4, 256));
-  prof_begin(PH_CSM, s);
-  const unsigned rb = (unsigned)((nrows + 3) / 4);
-  hipLaunchKernelGGL(k_ef_rows, dim3(rb), dim3(256), 0, s, mfcc, nrows, d_mfcc, 0, nullptr, sq_m);
-  ACOSS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ef_rows, dim3(rb), dim3(256), 0, s, ssm, nrows, d_ssm, 0, nullptr, sq_s);
-  ACOSS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ef_rows, dim3(rb), dim3(256), 0, s, chroma, nrows, d_chroma, 1, chn, nullptr);
-  ACOSS_LAUNCH_CHECK();
-  static const bool wave_tiles = getenv("ACOSS_EF_LDS_CSM") == nullptr;
-  const float* ssm_p = nullptr;  // SSM bank with rows padded to a multiple of 4 (k_ef_csm_w)
-  if (wave_tiles && d_ssm % 4 != 0) {
-    const int ldp = (int)align_up((size_t)d_ssm, 4);
-    float* pb = static_cast<float*>(workspace(15, (size_t)nrows * ldp * 4));
-    if (!pb) return ACOSS_E_HIP;
-    hipLaunchKernelGGL(k_ef_pad_rows, dim3(rb), dim3(256), 0, s, ssm, nrows, d_ssm, ldp, pb);
-    ACOSS_LAUNCH_CHECK();
-    ssm_p = pb;
-  }
-  prof_end(PH_CSM, s);
+  const EfBank B{mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, d_mfcc, d_ssm, d_chroma};
+  EfPrep R;
+  if (int rc = ef_prepare(B, s, &R)) return rc;
 
   // chunk of pairs: 3 CSMs (E overwrites the first), 4 binary matrices, 6 mean vectors, SW scratch
   const size_t mat = (size_t)ld * ld;
@@ -1297,12 +1361,6 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
   const size_t bin_lds = (size_t)ld * 4;
   const int64_t mstride = (int64_t)mat * chunk;       // between the 3 CSM planes
   const int64_t meanstride = (int64_t)ld * chunk;     // between the 3 mean vectors
-  const int tiles = (ld + kT - 1) / kT;  // LDS kernel tiles
-  // wave-tile CSMs: 32 x 32 tiles when every track has at most 64 blocks (Da-TACOS beat blocks:
-  // 14..47, a 64 x 64 tile there is mostly padding; profiles/r05/ef_short), 64 x 64 otherwise
-  const int wtile = ld <= 64 ? 32 : 64;
-  const int wtiles = (ld + wtile - 1) / wtile;
-  auto kw_euclid = wtile == 32 ? k_ef_csm_w<0, 32> : k_ef_csm_w<0, 64>;
   // one binarize block per (pair, matrix) when every track has at most 64 blocks (15,000 Da-TACOS-
   // shape songs: 4.04M -> 4.38M pairs/s, profiles/r05/ef_short/efbin15k_*.log)
   const bool small_bin = ld <= 64;
@@ -1314,16 +1372,6 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
   // column k-smallest means: 4 pairs per 256-thread block when every track has at most 64 blocks
   const int kmin_ppb = ld <= 64 ? 4 : 1;
   const unsigned kmin_gx = ld <= 64 ? 1u : (unsigned)((ld + 255) / 256);
-  auto kw_cosine = wtile == 32 ? k_ef_csm_w<1, 32> : k_ef_csm_w<1, 64>;
-  // short tracks: the cosine CSM with several consecutive pairs per wave sharing their query rows
-  // (k_ef_csm_w4); ACOSS_EF_W4=0 keeps one pair per wave
-  static const bool w4 = !(getenv("ACOSS_EF_W4") && getenv("ACOSS_EF_W4")[0] == '0');
-  // ... and the euclid CSMs with the reference columns of a query's run packed (k_ef_csm_pack):
-  // 32 x 64 tiles (pack_nb = 2) for every track up to 128 blocks; ACOSS_EF_PACK=1 takes 32 x 32
-  // tiles, 0 a tile per pair (Da-TACOS shapes, profiles/r06/ef_pack/README.txt: 14..47 blocks
-  // 4.85M -> 5.72M pairs/s, 30..80 blocks 1.12M -> 1.62M; 32 x 32 tiles 5.68M / 1.59M)
-  static const char* pack_env = getenv("ACOSS_EF_PACK");
-  const int pack_nb = ld > 128 || (pack_env && pack_env[0] == '0') ? 0 : pack_env && pack_env[0] == '1' ? 1 : 2;
   int ci = 0;
   for (int64_t p0 = 0; p0 < n_pairs; p0 += chunk, ++ci) {
     const int P = (int)((n_pairs - p0) < chunk ? (n_pairs - p0) : chunk);
@@ -1337,44 +1385,7 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
     int32_t* m_rows = sets[ci & (nset - 1)].m_rows;
     int32_t* m_cols = sets[ci & (nset - 1)].m_cols;
     int* oti = sets[ci & (nset - 1)].oti;
-    prof_begin(PH_CSM, st);
-    hipLaunchKernelGGL(k_ef_oti, dim3((P + 255) / 256), dim3(256), 0, st, chroma_med, pairs + 2 * p0, P, oti);
-    ACOSS_LAUNCH_CHECK();
-    {
-      const int n_tiles = tiles * tiles * P, n_wtiles = wtiles * wtiles * P;
-      auto euclid = [&](const float* bank, int d, const float* sq, float* dst) -> int {
-        if (wave_tiles && d % 4 != 0 && bank == ssm && ssm_p) {
-          bank = ssm_p;  // the row-padded copy made above
-          d = (int)align_up((size_t)d, 4);
-        }
-        if (wave_tiles && d % 4 == 0 && pack_nb) {
-          const int tw = 32 * pack_nb;
-          const int units = (P + kEfPack - 1) / kEfPack * ((ld + 31) / 32) * (kEfPack * ((ld + tw - 1) / tw));
-          hipLaunchKernelGGL(pack_nb == 1 ? k_ef_csm_pack<1> : k_ef_csm_pack<2>, dim3((unsigned)((units + 3) / 4)),
-                             dim3(256), 0, st, bank, d, sq, E, ld, P, units, dst);
-        } else if (wave_tiles && d % 4 == 0)
-          hipLaunchKernelGGL(kw_euclid, dim3((unsigned)((n_wtiles + 3) / 4)), dim3(256), 0, st, bank, d, sq, E, oti, ld,
-                             n_wtiles, dst);
-        else
-          hipLaunchKernelGGL(k_ef_csm<0>, dim3((unsigned)n_tiles), dim3(256), 0, st, bank, d, sq, E, oti, ld, dst);
-        ACOSS_LAUNCH_CHECK();
-        return ACOSS_OK;
-      };
-      if (euclid(mfcc, d_mfcc, sq_m, C) != ACOSS_OK || euclid(ssm, d_ssm, sq_s, C + mstride) != ACOSS_OK)
-        return ACOSS_E_HIP;
-    }
-    if (wave_tiles && d_chroma % 24 == 0 && w4 && wtile == 32) {
-      const int units = (P + kEfPPc - 1) / kEfPPc * wtiles * wtiles;
-      hipLaunchKernelGGL((k_ef_csm_w4<1, kEfPPc>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, st, chn, d_chroma,
-                         nullptr, E, oti, ld, P, units, C + 2 * mstride);
-    } else if (wave_tiles && d_chroma % 24 == 0)
-      hipLaunchKernelGGL(kw_cosine, dim3((unsigned)((wtiles * wtiles * P + 3) / 4)), dim3(256), 0, st, chn, d_chroma, nullptr, E,
-                         oti, ld, wtiles * wtiles * P, C + 2 * mstride);
-    else
-      hipLaunchKernelGGL(k_ef_csm<1>, dim3((unsigned)(tiles * tiles * P)), dim3(256), 0, st, chn, d_chroma, nullptr, E,
-                         oti, ld, C + 2 * mstride);
-    ACOSS_LAUNCH_CHECK();
-    prof_end(PH_CSM, st);
+    if (int rc = ef_launch_csms(B, R, pairs + 2 * p0, P, ld, oti, false, C, mstride, st)) return rc;
     prof_begin(PH_BIN, st);
     if (lane_bin)
       hipLaunchKernelGGL(k_ef_binarize_lanes, dim3((unsigned)((3 * P + 3) / 4)), dim3(256), 0, st, C, mstride, ld, E,

@@ -448,6 +448,52 @@ int acoss_earlyfusion_path(const float* mfcc, const float* ssm, const float* chr
                            double kappa, int32_t K, float mu, double* scores_out, int32_t* seg_out, int32_t path_cap,
                            int32_t* len_out, int32_t* path_out, void* hip_stream);
 
+/* EarlyFusion's per-pair similarity network fusion ("early SNF", Tralie 2017: the early fusion of
+ * the paper, which EarlyFusion.similarity's `early` score shortcuts) for a batch of pairs. Bank and
+ * pair arguments as acoss_earlyfusion. Pair p = (a, b), M and N blocks, n = M + N:
+ *  1. For each feature f in the order mfccs, ssms, chromas: CSM_f (M x N, float32) is the matrix
+ *     acoss_earlyfusion forms (euclid, euclid, blocked-OTI cosine); SSMA_f (M x M) and SSMB_f
+ *     (N x N) are the same distance of a track's blocks against themselves with no roll (get_ssm /
+ *     get_csm_cosine(X, X); the same kernels as CSM_f, once per track of a chunk).
+ *  2. W_f = getWCSMSSM(SSMA_f, SSMB_f, CSM_f, K, mu) (similarity_fusion.py:76-99): k1 =
+ *     int(K M / (M + N)), k2 = K - k1; all float32 (numpy's dtype rule), every exp the canonical
+ *     canon_expf. The CSM block is acoss_wcsm(CSM_f, k1, k2, mu). The SSM blocks follow getW
+ *     (:15-36) with k = k1 (A) or k2 (B): DSym = 0.5 (D + D^T) with a zero diagonal; MeanDist = the
+ *     mean of the k + 1 smallest of each row, added in ascending order, times (k + 1), over k;
+ *     Eps = ((MeanDist_i + MeanDist_j) + DSym) / 3; Denom = 2 (mu Eps)^2, a zero replaced by 1;
+ *     W = exp(-DSym^2 / Denom). The parent [[W_A, W_AB], [W_AB^T, W_B]] is float64 and holds the
+ *     float32 values exactly.
+ *  3. F = doSimilarityFusionWs([W_mfccs, W_ssms, W_chromas], K, niters, reg_diag) (:146-186), all
+ *     float64: getP divides each row by its sum (columns added in ascending order; a zero sum is
+ *     replaced by 1); getS keeps the K largest of each row of W, self included, the lowest column
+ *     among equal values, divided by their sum (added in ascending column order; zero -> 1). A step
+ *     for matrix i is S_i ((sum of the other two) / 2) S_i^T + reg_diag I (reg_diag > 0), both
+ *     products summed over the K neighbours in ascending column order from +0, one rounded
+ *     multiply and add per term. The first round reads the three P only; from the second round on
+ *     matrix i sees the new matrices k < i (the reference's `Pts = nextPts` aliasing). F is
+ *     (((0 + P_0) + P_1) + P_2) / 3; niters = 0 gives the mean of the three P.
+ *  4. cross = F[:M, M:] + F[M:, :M]^T (M x N). The binary matrix has nn ones per row at the nn
+ *     LARGEST values of cross, ties to the lowest column, nn = csm_to_binary's count for kappa and
+ *     N: csm_to_binary(exp(-cross), kappa) up to where a float64 exp merges two values.
+ *     score_out[p] = smith_waterman_constrained of that matrix: acoss_sw_constrained's bits.
+ * A pair the reference cannot fuse (it raises) breaks 1 <= k1 <= M - 2, 1 <= k2 <= N - 2 or K < n:
+ * it scores NaN and writes NaN over its range of cross_out; the other pairs are untouched and the
+ * call returns ACOSS_OK.
+ * score_out: double[n_pairs]. cross_out: NULL, or pair p's M x N matrix, row-major, at
+ * cross_out[cross_off[p] ..); cross_off: int64[n_pairs + 1], checked on the device before any
+ * write (negative, shorter than M N, or past cross_total: ACOSS_E_ARG naming the first bad pair).
+ * ACOSS_E_ARG as acoss_earlyfusion, and for niters < 0, reg_diag < 0, K > 64, a track of more than
+ * 512 blocks or a pair naming a track outside [0, n_tracks). Pairs with n <= 101 run all their
+ * 3 niters steps in one workgroup with two n x n float64 matrices in LDS (16 n^2 <= 160 KB);
+ * longer ones keep their matrices in the workspace, chunked under ACOSS_EF_BYTES. The operations
+ * and their order are the same in both, so a pair's output depends neither on its place in the
+ * list nor on the chunking; a pair listed twice gives the same bits twice. */
+int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                          const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                          int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
+                          double kappa, int32_t K, float mu, int32_t niters, double reg_diag, double* score_out,
+                          const int64_t* cross_off, int64_t cross_total, double* cross_out, void* hip_stream);
+
 /* EarlyFusion beat-synchronous block features of a batch of tracks (replaces
  * EarlyFusion.load_features' block loops, acoss/algorithms/earlyfusion_traile.py:67-154, and its
  * skimage resize_block, :214-247, restated in float64). Track t: chroma frames [frame_off[t],
