@@ -395,15 +395,6 @@ __global__ __launch_bounds__(256) void k_efs_binarize(const double* __restrict__
   for (int c = threadIdx.x; c < N; c += 256) o[c] = (uint16_t)bits[c];
 }
 
-__global__ void k_efs_swmeta(EfPairs E, int P, int32_t* rows, int32_t* cols) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P) return;
-  int a, b, M, N;
-  pair_dims(E, p, &a, &b, &M, &N);
-  rows[p] = M;
-  cols[p] = N;
-}
-
 __global__ void k_efs_refused(EfPairs E, int P, int K, double* __restrict__ score) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
@@ -424,13 +415,10 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
                                      int32_t niters, double reg_diag, double* score_out, const int64_t* cross_off,
                                      int64_t cross_total, double* cross_out, void* hip_stream) {
   clear_error();
-  if (n_tracks <= 0 || n_pairs < 0 || max_blocks <= 0 || d_mfcc <= 0 || d_ssm <= 0 || d_chroma <= 0 ||
-      d_chroma % 12 != 0 || K <= 0 || K >= max_blocks + 1 || kappa < 0.0 || niters < 0 || !(reg_diag >= 0.0) ||
-      (n_pairs > 0 && (!mfcc || !ssm || !chroma || !chroma_med || !block_off || !n_blocks || !pairs || !score_out)) ||
-      (cross_out && (!cross_off || cross_total < 0))) {
-    set_error("acoss_earlyfusion_snf: bad arguments");
-    return ACOSS_E_ARG;
-  }
+  const EfBank B{mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, d_mfcc, d_ssm, d_chroma};
+  if (int rc = ef_check_args("acoss_earlyfusion_snf", B, max_blocks, pairs, n_pairs, kappa, K, score_out,
+                             niters < 0 || !(reg_diag >= 0.0) || (cross_out && (!cross_off || cross_total < 0))))
+    return rc;
   const int ld = (int)align_up((size_t)max_blocks, 4);
   if (2 * ld > kEfsNmax || K > kEfsKmax) {
     set_error("acoss_earlyfusion_snf: more than %d blocks in a track or K above %d", kEfsNmax / 2, kEfsKmax);
@@ -463,7 +451,6 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
       set_error("acoss_earlyfusion_snf: a pair names a track outside [0, %d)", n_tracks);
       return ACOSS_E_ARG;
     }
-  const EfBank B{mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, d_mfcc, d_ssm, d_chroma};
   EfPrep R;
   if (int rc = ef_prepare(B, s, &R)) return rc;
 
@@ -476,9 +463,7 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
   const size_t sw_b = sw_bnd_bytes(ld, ld);
   const size_t per_pair = 3 * mat * 4 + 2 * 3 * mat * 4 + 3 * 4 * (size_t)ld * 4 + 7 * n2 * 8 +
                           3 * (size_t)K * ldn * 12 + mat * 8 + (size_t)wplane * 2 + sw_b + 64;
-  size_t budget = (size_t)4 << 30;
-  if (const char* e = getenv("ACOSS_EF_BYTES")) budget = strtoull(e, nullptr, 10);
-  int64_t chunk = (int64_t)(budget / per_pair);
+  int64_t chunk = (int64_t)(ef_chunk_budget() / per_pair);
   if (chunk < 1) chunk = 1;
   if (chunk > 32768) chunk = 32768;
   if (chunk > n_pairs) chunk = n_pairs;
@@ -613,8 +598,7 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
     ACOSS_LAUNCH_CHECK();
     prof_end(PH_BIN, s);
     prof_begin(PH_SW, s);
-    hipLaunchKernelGGL(k_efs_swmeta, dim3((P + 255) / 256), dim3(256), 0, s, E, P, m_rows, m_cols);
-    ACOSS_LAUNCH_CHECK();
+    if (int rc = ef_launch_swmeta(E, P, 1, m_rows, m_cols, s)) return rc;
     if (int rc = launch_swb_batch(Wb, wplane, ld, m_rows, m_cols, P, ld, ld, bnd, score_out + p0, s)) return rc;
     hipLaunchKernelGGL(k_efs_refused, dim3((P + 255) / 256), dim3(256), 0, s, E, P, (int)K, score_out + p0);
     ACOSS_LAUNCH_CHECK();
