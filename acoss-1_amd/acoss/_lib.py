@@ -947,7 +947,8 @@ def ef_snf_cross_offsets(nb, pairs):
 
 
 def ef_snf_check_args(kappa, K, niters, reg_diag, max_blocks=None):
-    """The argument errors of earlyfusion_snf that need no GPU (ValueError)."""
+    """The argument errors of earlyfusion_snf that need no GPU (ValueError). K is held to [1, 64]
+    whatever max_blocks is: each pair answers for it on its own (ef_snf_pair_ok)."""
     if int(niters) != niters or niters < 0:
         raise ValueError("niters must be a non-negative integer, got %r" % (niters,))
     if not reg_diag >= 0:

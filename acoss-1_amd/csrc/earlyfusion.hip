@@ -519,7 +519,7 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
                int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
   clear_error();
   const EfBank B{mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, d_mfcc, d_ssm, d_chroma};
-  if (int rc = ef_check_args(entry, B, max_blocks, pairs, n_pairs, kappa, K, scores_out,
+  if (int rc = ef_check_args(entry, B, max_blocks, pairs, n_pairs, kappa, K, max_blocks, scores_out,
                              n_pairs > 0 && ((stage == EF_LOCATE && !seg_out) ||
                                              (stage == EF_PATH && (!len_out || !path_out)))))
     return rc;

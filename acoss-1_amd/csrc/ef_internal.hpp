@@ -31,12 +31,14 @@ struct EfBank {
   int32_t n_tracks, d_mfcc, d_ssm, d_chroma;
 };
 
-// The bank and pair arguments every EarlyFusion entry takes; `own_bad`: what the entry checks
-// beyond them. Sets "<entry>: bad arguments" and returns ACOSS_E_ARG when anything is off.
+// The bank and pair arguments every EarlyFusion entry takes; `k_max`: the largest K of the entry
+// (max_blocks where getWCSM(K, K) runs on the CSM itself, the lane limit for early SNF, whose pairs
+// answer for K one by one); `own_bad`: what the entry checks beyond them. Sets "<entry>: bad
+// arguments" and returns ACOSS_E_ARG when anything is off.
 inline int ef_check_args(const char* entry, const EfBank& B, int32_t max_blocks, const int32_t* pairs, int64_t n_pairs,
-                         double kappa, int32_t K, const double* scores_out, bool own_bad) {
+                         double kappa, int32_t K, int32_t k_max, const double* scores_out, bool own_bad) {
   if (B.n_tracks <= 0 || n_pairs < 0 || max_blocks <= 0 || B.d_mfcc <= 0 || B.d_ssm <= 0 || B.d_chroma <= 0 ||
-      B.d_chroma % 12 != 0 || K <= 0 || K >= max_blocks + 1 || kappa < 0.0 || own_bad ||
+      B.d_chroma % 12 != 0 || K <= 0 || K > k_max || kappa < 0.0 || own_bad ||
       (n_pairs > 0 && (!B.mfcc || !B.ssm || !B.chroma || !B.chroma_med || !B.block_off || !B.n_blocks || !pairs ||
                        !scores_out))) {
     set_error("%s: bad arguments", entry);

@@ -416,12 +416,14 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
                                      int64_t cross_total, double* cross_out, void* hip_stream) {
   clear_error();
   const EfBank B{mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, d_mfcc, d_ssm, d_chroma};
-  if (int rc = ef_check_args("acoss_earlyfusion_snf", B, max_blocks, pairs, n_pairs, kappa, K, score_out,
+  // K against the lane limit only, whatever max_blocks is: the reference needs K < M + N, k1 <= M - 2
+  // and k2 <= N - 2 of each pair (snf_split), and a pair that breaks them scores NaN on its own
+  if (int rc = ef_check_args("acoss_earlyfusion_snf", B, max_blocks, pairs, n_pairs, kappa, K, kEfsKmax, score_out,
                              niters < 0 || !(reg_diag >= 0.0) || (cross_out && (!cross_off || cross_total < 0))))
     return rc;
   const int ld = (int)align_up((size_t)max_blocks, 4);
-  if (2 * ld > kEfsNmax || K > kEfsKmax) {
-    set_error("acoss_earlyfusion_snf: more than %d blocks in a track or K above %d", kEfsNmax / 2, kEfsKmax);
+  if (2 * ld > kEfsNmax) {
+    set_error("acoss_earlyfusion_snf: more than %d blocks in a track", kEfsNmax / 2);
     return ACOSS_E_ARG;
   }
   if (n_pairs == 0) return ACOSS_OK;

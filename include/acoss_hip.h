@@ -482,9 +482,13 @@ int acoss_earlyfusion_path(const float* mfcc, const float* ssm, const float* chr
  * score_out: double[n_pairs]. cross_out: NULL, or pair p's M x N matrix, row-major, at
  * cross_out[cross_off[p] ..); cross_off: int64[n_pairs + 1], checked on the device before any
  * write (negative, shorter than M N, or past cross_total: ACOSS_E_ARG naming the first bad pair).
- * ACOSS_E_ARG as acoss_earlyfusion, and for niters < 0, reg_diag < 0, K > 64, a track of more than
- * 512 blocks or a pair naming a track outside [0, n_tracks). Pairs with n <= 101 run all their
- * 3 niters steps in one workgroup with two n x n float64 matrices in LDS (16 n^2 <= 160 KB);
+ * K: 1 <= K <= 64 whatever max_blocks is (acoss_earlyfusion's K <= max_blocks does not apply: K is
+ * weighed against each pair's own M and N by the three conditions above, so K = 50 on a bank of
+ * 47-block tracks fuses every pair that meets them).
+ * ACOSS_E_ARG as acoss_earlyfusion but for that K rule, and for niters < 0, reg_diag < 0, K > 64, a
+ * track of more than 512 blocks or a pair naming a track outside [0, n_tracks). Pairs with
+ * n <= 101 run all their 3 niters steps in one workgroup with two n x n float64 matrices in LDS
+ * (16 n^2 <= 160 KB);
  * longer ones keep their matrices in the workspace, chunked under ACOSS_EF_BYTES. The operations
  * and their order are the same in both, so a pair's output depends neither on its place in the
  * list nor on the chunking; a pair listed twice gives the same bits twice. */

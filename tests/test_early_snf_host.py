@@ -1,6 +1,7 @@
 """The numpy restatement of the per-pair similarity network fusion (tests/early_snf_np.py) against
 the reference's own run (tests/golden/early_snf_golden.npz, made by make_golden_early_snf.py), the
-pair conditions, and the binding's argument checks. No GPU.
+pair conditions, the binding's argument checks, and the inputs of the GPU tests' cases
+(early_snf_cases.py: finite restatement, the refused pairs, the stable share). No GPU.
 
 The golden inputs are float64, so the reference and the restatement differ only in numpy's
 summation order (np.partition's order inside np.mean, pairwise np.sum): affinities and fused
@@ -94,6 +95,70 @@ def test_binding_rejects_bad_arguments_without_a_gpu():
     with pytest.raises(ValueError):
         _lib.ef_snf_cross_offsets(nb, [[0, 3]])
     assert "acoss_earlyfusion_snf" in _lib.SIGNATURES and len(_lib.SIGNATURES["acoss_earlyfusion_snf"]) == 23
+
+
+def test_k_is_weighed_per_pair_not_against_max_blocks():
+    """K = 50 on a 47-block bank and K = 64 on two 40-block tracks fuse in the reference's terms; the
+    host check holds K to [1, 64] whatever max_blocks is."""
+    from acoss import _lib
+    assert es.pair_ok(47, 47, 50) and es.pair_ok(40, 40, 64) and es.split(40, 40, 64) == (32, 32)
+    assert bool(_lib.ef_snf_pair_ok(47, 47, 50)) and bool(_lib.ef_snf_pair_ok(40, 40, 64))
+    for K, mb in ((50, 47), (64, 40), (64, 1)):
+        _lib.ef_snf_check_args(0.1, K, 5, 1.0, mb)
+    with pytest.raises(ValueError):
+        _lib.ef_snf_check_args(0.1, 65, 5, 1.0, 512)
+
+
+# ---- the inputs of test_gpu_early_snf_banks.py and test_gpu_early_snf_params.py, checked without a
+# GPU: what those tests conclude rests on these conditions of the restatement alone
+@pytest.mark.parametrize("name", ["tiny", "short", "mid", "long"])
+def test_bank_cases_rest_on_sound_inputs(name):
+    import early_snf_cases as ec
+    feats, pairs, refs = ec.bank_case(name)
+    blocks = ec.BANKS[name][0]
+    assert [len(f["mfccs"]) for f in feats] == list(blocks)
+    if name == "long":
+        assert [sum(ec.shape_of(feats, p)) for p in pairs] == [1024, 812, 812, 80]
+    else:
+        assert len(pairs) == len(blocks) ** 2 and len({tuple(p) for p in pairs}) == len(pairs)
+    ec.check_inputs(feats, pairs, refs, ec.BANK_K, label=name)  # K = 10 refuses none of these shapes
+
+
+@pytest.mark.parametrize("name", ["short", "mid"])
+def test_float_bank_cases_rest_on_sound_inputs(name):
+    import early_snf_cases as ec
+    feats, pairs, refs = ec.float_case(name)
+    shapes = [ec.shape_of(feats, p) for p in pairs]
+    want = {"short": [(14, 47), (47, 14), (22, 23), (31, 31)], "mid": [(64, 101), (128, 100), (30, 128)]}[name]
+    assert 6 <= len(pairs) <= 9 and all(s in shapes for s in want)
+    for f in feats:  # general float32 values, not the integer-exact ones
+        assert f["mfccs"].dtype == np.float32 and not np.array_equal(f["mfccs"], np.rint(f["mfccs"]))
+        assert (f["ssms"] >= 0).all() and (f["chromas"] >= 0).all() and (f["chroma_med"] >= 0).all()
+    ec.check_inputs(feats, pairs, refs, ec.BANK_K, label="float-" + name)
+
+
+def test_parameter_rows_rest_on_sound_inputs():
+    import early_snf_cases as ec
+    assert len(ec.PARAM_ROWS) == 14 and len(set(ec.PARAM_ROWS)) == 14
+    assert sorted({r.K for r in ec.PARAM_ROWS}) == [2, 3, 10, 11, 50, 64]
+    for row in ec.PARAM_ROWS:
+        feats, pairs, refs = ec.param_case(row)
+        assert [ec.shape_of(feats, p) for p in pairs] == ec.PARAM_SHAPES
+        ec.check_inputs(feats, pairs, refs, row.K, refused=ec.PARAM_REFUSED.get(row.K, ()), label=ec.row_id(row))
+    for K in (50, 64):
+        feats, pairs, refs = ec.k_above_blocks_case(K)
+        ec.check_inputs(feats, pairs, refs, K, label="K above max_blocks")
+
+
+def test_duplicate_block_case_stays_finite_in_the_restatement():
+    import early_snf_cases as ec
+    feats, pairs, refs = ec.duplicate_block_case()
+    d = es.distances(feats[0], feats[1])
+    assert all(not t[0].any() for t in d)  # the twelve identical blocks: all self distances zero
+    for r in refs:
+        assert r["bound"] is not None and np.isfinite(r["bound"])
+        assert np.isfinite(r["canon"]["cross"]).all() and np.isfinite(r["numpy"]["cross"]).all()
+        assert all(np.isfinite(W).all() for W in r["canon"]["W"])
 
 
 def test_plugin_option_is_off_by_default():

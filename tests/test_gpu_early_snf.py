@@ -23,6 +23,7 @@ import pytest
 
 import early_snf_np as es
 import oracle
+from early_snf_cases import make_bank, pair_tracks, references, rel_dev
 from test_gpu_earlyfusion_pin import _clique_blocks, _cover
 
 pytestmark = pytest.mark.gpu
@@ -33,61 +34,22 @@ SHAPES = [(12, 12), (14, 47), (47, 14), (32, 32), (32, 33), (50, 51), (51, 51), 
 SEED = 7
 
 
-def rel_dev(a, b):
-    return float(np.max(np.abs(a - b) / np.abs(b)))
-
-
 def top_binary(cross, kappa):
     return es.binarize_top(cross, kappa)
 
 
 def build_case():
-    """(feats, pairs, refs): refs[p] = {"canon", "numpy": early_snf results, "bound", "stable"}."""
-    rng = np.random.Generator(np.random.PCG64(SEED))
-    feats, pairs = [], []
-    for M, N in SHAPES:
-        base = _clique_blocks(rng, max(M, N) + 10)
-        for nb in (M, N):
-            bf = _cover(rng, base, nb)
-            bf["chroma_med"] = rng.permutation(12).astype(np.float32)
-            feats.append(bf)
-        pairs.append((len(feats) - 2, len(feats) - 1))
+    """(feats, pairs, refs): refs[p] = {"canon", "numpy": early_snf results, "bound", "stable"}
+    (early_snf_cases.py)."""
+    feats, pairs = pair_tracks(SHAPES, SEED)
     pairs.append(pairs[1])  # a duplicated pair
     pairs = np.array(pairs, np.int32)
-    refs, cache = [], {}
-    for a, b in pairs:
-        if (a, b) not in cache:
-            d = es.distances(feats[a], feats[b])
-            canon = es.early_snf(d, KAPPA, K, NITERS, ev=es.CANON)
-            other = es.early_snf(d, KAPPA, K, NITERS, ev=es.NUMPY)
-            r = {"canon": canon, "numpy": other, "bound": None, "stable": False}
-            if canon["binary"] is not None:
-                r["bound"] = 8 * rel_dev(other["cross"], canon["cross"])
-                nn = es.nneighbs(KAPPA, canon["cross"].shape[1])
-                s = -np.sort(-canon["cross"], 1)
-                gap = float(np.min((s[:, nn - 1] - s[:, nn]) / np.abs(s[:, nn - 1])))
-                r["stable"] = bool(np.array_equal(canon["binary"], other["binary"]) and gap > r["bound"])
-            cache[(a, b)] = r
-        refs.append(cache[(a, b)])
-    return feats, pairs, refs
+    return feats, pairs, references(feats, pairs, KAPPA, K, NITERS)
 
 
 @pytest.fixture(scope="module")
 def case():
     return build_case()
-
-
-def make_bank(feats):
-    import torch
-    nb = np.array([len(f["mfccs"]) for f in feats], np.int32)
-    off = np.zeros(len(feats), np.int64)
-    off[1:] = np.cumsum(nb[:-1])
-    host = {k: np.concatenate([f[k] for f in feats]).astype(np.float32) for k in ("mfccs", "ssms", "chromas")}
-    host["chroma_med"] = np.stack([f["chroma_med"] for f in feats]).astype(np.float32)
-    host["nb"], host["off"] = nb, off
-    bank = {k: torch.as_tensor(host[k]).cuda() for k in host}
-    bank["nb_host"], bank["max_blocks"] = nb, int(nb.max())
-    return bank, host
 
 
 @pytest.fixture(scope="module")
