@@ -57,6 +57,9 @@ SIGNATURES = {
     "acoss_crp_path_dmax": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _vp, _vp, _vp, _i32, _vp,
                             _vp, _vp],
     "acoss_path_crp_dmax": [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp, _vp, _vp],
+    "acoss_crp_rqa": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams), _i32, _vp, _vp, _vp, _vp, _vp,
+                      _i32, _vp, _vp],
+    "acoss_rqa_crp": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "acoss_sw_constrained": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "acoss_sw_locate": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "acoss_sw_path": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp],
@@ -392,6 +395,48 @@ def path_crp(C, gamma_open=0.5, gamma_ext=0.5, path_cap=None, align=0):
                                         stream)
     _check(rc, entry)
     return out, seg, padded[:int(n.item())]
+
+
+RQA_COUNTS = ("n_rec", "n_lines", "n_lines_min", "n_pts_min")  # columns of "counts"
+RQA_STATS = ("rr", "det", "lmean", "entr")                      # columns of "stats"
+
+
+def crp_rqa(feats, track_off, track_len, max_len, pairs, params, lmin=2, smax=True, hist_cap=0, lines=True):
+    """Batched cross-recurrence quantification (acoss_crp_rqa; the definition: include/acoss_hip.h):
+    inputs as crp_align. Returns device tensors {"counts" (P, 4) i64 = RQA_COUNTS, "lmax" (P,) i32,
+    "stats" (P, 4) f64 = RQA_STATS, "oti" (P,) i32, with smax "smax" (P,) f32, with hist_cap > 0
+    "hist" (P, hist_cap) i32, hist[p, l] = the number of diagonal lines of length l}. lines=False
+    leaves "counts", "lmax" and "stats" out and skips the line walk unless a histogram is asked for."""
+    keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
+    out = {"oti": _empty("int32", P)}
+    if lines:
+        out.update(counts=_empty("int64", P, 4), lmax=_empty("int32", P), stats=_empty("float64", P, 4))
+    if smax:
+        out["smax"] = _empty("float32", P)
+    if hist_cap:
+        out["hist"] = _empty("int32", P, int(hist_cap))
+    rc = load_library().acoss_crp_rqa(*lead, int(lmin), _ptr(out.get("counts")), _ptr(out.get("lmax")),
+                                      _ptr(out.get("stats")), _ptr(out.get("smax")), _ptr(out["oti"]), int(hist_cap),
+                                      _ptr(out.get("hist")), _stream())
+    _check(rc, "acoss_crp_rqa")
+    return out
+
+
+def rqa_crp(C, lmin=2, smax=True, hist=False):
+    """Cross-recurrence quantification of a binary (M, N) matrix (acoss_rqa_crp): device tensors
+    {"counts" (4,) i64, "lmax" (1,) i32, "stats" (4,) f64, with smax "smax" (1,) f32, with hist
+    "hist" i32}. hist=True returns every bin, min(M, N) + 1 entries; an integer the first that many."""
+    C, M, N, _, _, stream = _matrix_args(C, 0.0, 0.0)
+    cap = 0 if hist is False else (min(M, N) + 1 if hist is True else int(hist))
+    out = {"counts": _empty("int64", 4), "lmax": _empty("int32", 1), "stats": _empty("float64", 4)}
+    if smax:
+        out["smax"] = _empty("float32", 1)
+    if cap:
+        out["hist"] = _empty("int32", cap)
+    rc = load_library().acoss_rqa_crp(_ptr(C), M, N, int(lmin), _ptr(out["counts"]), _ptr(out["lmax"]),
+                                      _ptr(out["stats"]), _ptr(out.get("smax")), cap, _ptr(out.get("hist")), stream)
+    _check(rc, "acoss_rqa_crp")
+    return out
 
 
 def _pack_mats(mats, dtype):

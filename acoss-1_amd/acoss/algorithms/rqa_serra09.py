@@ -121,36 +121,90 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
                 "path_off": r["path_off"].cpu().numpy(), "path_cells": pc,
                 "path_frames": path_frames(pc, self.tau, self.downsample_fac)}
 
+    def _rqa_dev(self, idxs, lmin=2, smax=True, hist_cap=0, lines=True):
+        self.prepare()
+        return self._bank.crp_rqa(np.asarray(idxs, np.int32).reshape(-1, 2), m=self.m, tau=self.tau, kappa=self.kappa,
+                                  oti=self.oti, lmin=lmin, smax=smax, hist_cap=hist_cap, lines=lines)
+
+    def rqa(self, idxs, lmin=2, hist=False):
+        """Cross-recurrence quantification of every (query, reference) pair of idxs (the definition:
+        include/acoss_hip.h, acoss_crp_rqa): a dict of host arrays, each (P,): 'rr', 'det', 'lmean',
+        'entr' (float64), 'lmax' (int32), 'smax' (float32), 'n_rec', 'n_lines', 'n_lines_min',
+        'n_pts_min' (int64) and 'oti'. lmin: the shortest diagonal line that 'det', 'lmean', 'entr'
+        and the two '_min' counts take. hist=True adds 'hist' (P, L + 1) int32, L the longest stacked
+        length of the bank: hist[p, l] = the number of diagonal lines of length l in pair p's CRP.
+        Not collective: a rank quantifies the pairs it is given."""
+        self.prepare()
+        cap = _lib.stacked_len(self._bank.max_len, self.m, self.tau) + 1 if hist else 0
+        r = {k: v.cpu().numpy() for k, v in self._rqa_dev(idxs, lmin=lmin, hist_cap=cap).items()}
+        out = {k: r["stats"][:, c] for c, k in enumerate(_lib.RQA_STATS)}
+        out.update({k: r["counts"][:, c] for c, k in enumerate(_lib.RQA_COUNTS)})
+        out.update(lmax=r["lmax"], smax=r["smax"], oti=r["oti"])
+        if hist:
+            out["hist"] = r["hist"]
+        return out
+
     def _norm_factors(self):
         """sqrt(n_j) in float64, n_j = downsampled frames of song j."""
         return np.sqrt(np.array([self.load_features(j).shape[0] for j in range(self.N)], np.float64))
 
 
 class Serra09(ChromaBackedAlgorithm):
+    # what all_pairwise can fill Ds with: the paper's three maxima, which grow with the tracks, and
+    # the intensive CRQA measures, which do not
+    MAXIMA = ("qmax", "smax", "lmax")
+    MEASURES = MAXIMA + ("det", "lmean", "entr", "rr")
+
+    @classmethod
+    def algorithm_name(cls, measure="qmax"):
+        """The name under which a Serra09 that scores by `measure` keeps its Ds cache and writes its
+        results: 'Serra09' for Qmax (the reference's), 'Serra09-<measure>' for any other."""
+        if measure not in cls.MEASURES:
+            raise ValueError("measure must be one of %s, not %r" % (", ".join(cls.MEASURES), measure))
+        return "Serra09" if measure == "qmax" else "Serra09-%s" % measure
+
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='benchmark', oti=True, kappa=0.095,
-                 tau=1, m=9, downsample_fac=40, cachedir="cache"):
+                 tau=1, m=9, downsample_fac=40, cachedir="cache", measure="qmax", lmin=2):
+        name = self.algorithm_name(measure)
+        if int(lmin) != lmin or lmin < 1:
+            raise ValueError("lmin must be an integer >= 1, not %r" % (lmin,))
+        self.measure = measure
+        self.lmin = int(lmin)
         self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac)
-        CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name="Serra09", datapath=datapath, shortname=shortname,
+        CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name=name, datapath=datapath, shortname=shortname,
                                 cachedir=cachedir)
 
+    def _measure_dev(self, idxs):
+        """The (P,) float32 device scores of the pairs by self.measure."""
+        if self.measure == "qmax":
+            return self._score_dev(idxs)["qmax"]
+        if self.measure == "smax":
+            return self._rqa_dev(idxs, lines=False)["smax"]
+        r = self._rqa_dev(idxs, lmin=self.lmin, smax=False)
+        if self.measure == "lmax":
+            return r["lmax"].float()
+        return r["stats"][:, _lib.RQA_STATS.index(self.measure)].float()
+
     def similarity(self, idxs):
-        """Qmax of every (query, reference) pair into every Ds key (rqa_serra09.py:55-69)."""
+        """Qmax (or self.measure) of every (query, reference) pair into every Ds key (rqa_serra09.py:55-69)."""
         idxs = np.asarray(idxs)
         if len(idxs) == 0:
             return
-        q = self._score(idxs)["qmax"]
+        q = self._measure_dev(idxs).cpu().numpy()
         for key in self.Ds.keys():
             self.Ds[key][idxs[:, 0], idxs[:, 1]] = q
 
     def _device_scores(self, idxs):
-        q = self._score_dev(idxs)["qmax"]
+        q = self._measure_dev(idxs)
         return {key: q for key in self.Ds}
 
     def normalize_by_length(self):
         """D[i, j] /= sqrt(n_j), n_j = downsampled frames of song j (rqa_serra09.py:71-83);
         the quotient is taken in float64 and stored in the float32 matrix, as the reference
-        (acoss_ds_finish mode 'serra09')."""
-        self._finish_device(self._norm_factors(), "serra09")
+        (acoss_ds_finish mode 'serra09'). The three maxima grow with the tracks and are divided; the
+        intensive measures (rr, det, lmean, entr) are left as they are."""
+        if self.measure in self.MAXIMA:
+            self._finish_device(self._norm_factors(), "serra09")
 
 
 def parser_args(args):

@@ -24,12 +24,14 @@ shortlist_algorithms = ("Serra09", "SiMPle")  # the alignment scorers that take 
 
 
 def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09", shortname="covers80",
-              parallel=True, n_workers=-1, cachedir="cache", shortlist=None):
+              parallel=True, n_workers=-1, cachedir="cache", shortlist=None, measure="qmax"):
     """Run one cover-ID algorithm over a dataset CSV and print/write its evaluation statistics.
     Returns the algorithm object (its Ds hold the similarity matrices).
     shortlist: None, or k: Serra09 / SiMPle score only each song's k best FTM2D candidates (shingles
     made from the same CSV, features, chroma type and cache directory); the entries of Ds they do
-    not score are -inf."""
+    not score are -inf.
+    measure: what Serra09 fills Ds with, one of Serra09.MEASURES ('qmax', the reference's, 'smax', 'lmax',
+    'det', 'lmean', 'entr', 'rr'); any other than 'qmax' runs, caches and reports as 'Serra09-<measure>'."""
     logger = log(_LOG_FILE_PATH)
     if algorithm not in algorithm_names and algorithm != "EarlyFusion":
         warn = ("acoss.coverid: Couldn't find '%s' algorithm in acoss Available cover id algorithms are %s "
@@ -39,6 +41,8 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
     if shortlist is not None and algorithm not in shortlist_algorithms:
         raise ValueError("shortlist is supported by %s only, not by '%s'"
                          % (" and ".join(shortlist_algorithms), algorithm))
+    if measure != "qmax" and algorithm != "Serra09":
+        raise ValueError("measure is supported by Serra09 only, not by '%s'" % algorithm)
     logger.info("Running acoss cover identification benchmarking for the algorithm - '%s'" % algorithm)
     start = time.monotonic()
     kw = dict(dataset_csv=dataset_csv, datapath=feature_dir, chroma_type=feature_type, shortname=shortname,
@@ -55,7 +59,7 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         del first
     if algorithm == "Serra09":
         from .algorithms.rqa_serra09 import Serra09
-        algo = Serra09(**kw)
+        algo = Serra09(measure=measure, **kw)
         logger.info('Computing pairwise similarity...')
         algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True, candidates=candidates)
         algo.normalize_by_length()

@@ -156,3 +156,17 @@ class ChromaBank:
         "dmax"; its steps also include (1, 0) and (0, 1) and i0 or j0 may be 1 (_lib.crp_path)."""
         empty = self._located(align) + (("path_off", 1, "int64"), ("cells", (0, 2), "int32"))
         return self._crp(_lib.crp_path, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext), align=align)
+
+    def crp_rqa(self, pairs, m=9, tau=1, kappa=0.095, oti=True, lmin=2, smax=True, hist_cap=0, lines=True):
+        """Cross-recurrence quantification of (query, reference) pairs: {"counts" (P, 4), "lmax",
+        "stats" (P, 4), "oti"} device tensors, with smax "smax", with hist_cap > 0 "hist"
+        (P, hist_cap) (see _lib.crp_rqa); the CRP is crp_align's. lines=False: "oti" and "smax" only."""
+        empty = [("oti", 0, "int32")]
+        if lines:
+            empty += [("counts", (0, 4), "int64"), ("lmax", 0, "int32"), ("stats", (0, 4), "float64")]
+        if smax:
+            empty.append(("smax", 0, "float32"))
+        if hist_cap:
+            empty.append(("hist", (0, int(hist_cap)), "int32"))
+        return self._crp(_lib.crp_rqa, empty, pairs, (m, tau, kappa, oti, 0.5, 0.5), lmin=lmin, smax=smax,
+                         hist_cap=hist_cap, lines=lines)

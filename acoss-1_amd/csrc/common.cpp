@@ -109,7 +109,7 @@ PhaseRec g_open[PH_COUNT];
 const char* kPhaseNames[PH_COUNT] = {"prep",      "oti",     "select_rows", "select_cols", "crp_mask", "dp_qmax",
                                      "dp_dmax",   "sw",      "csm",         "binarize",    "wcsm",     "simple_mp",
                                      "sweep",     "ftm_sync", "ftm_dft",    "ftm_median",  "ftm_scores", "dp_trace",
-                                     "dp_dir",    "backtrack", "snf"};
+                                     "dp_dir",    "backtrack", "snf",    "rqa"};
 hipEvent_t get_event() {
   if (!g_pool.empty()) {
     hipEvent_t e = g_pool.back();

@@ -23,7 +23,7 @@ hipEvent_t sync_event(int idx);  // per-device timing-free events for cross-stre
 // through acoss_profile_read). Phases are small integers; names in common.cpp.
 enum Phase { PH_PREP = 0, PH_OTI, PH_SEL_ROWS, PH_SEL_COLS, PH_MASK, PH_DP_QMAX, PH_DP_DMAX, PH_SW, PH_CSM,
              PH_BIN, PH_WCSM, PH_SIMPLE, PH_SWEEP, PH_FTM_SYNC, PH_FTM_DFT, PH_FTM_MEDIAN, PH_FTM_SCORES,
-             PH_DP_TRACE, PH_DP_DIR, PH_BACKTRACK, PH_SNF, PH_COUNT };
+             PH_DP_TRACE, PH_DP_DIR, PH_BACKTRACK, PH_SNF, PH_RQA, PH_COUNT };
 bool profiling();
 void prof_begin(int phase, hipStream_t s);
 void prof_end(int phase, hipStream_t s);

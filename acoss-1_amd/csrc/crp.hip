@@ -495,6 +495,9 @@ enum CrpSlot {
   SLOT_LOCATE = 22, SLOT_LOCATE_CRP = 23,
   // the direction DP's plane, band-boundary records and end keys, likewise: acoss_crp_path, acoss_path_crp
   SLOT_PATH = 24, SLOT_PATH_CRP = 25,
+  // the line walk's band-boundary records, likewise: acoss_crp_rqa; acoss_rqa_crp after its MatrixView,
+  // followed by the Smax DP's
+  SLOT_RQA = 29, SLOT_RQA_CRP = 30,
 };
 
 int check_params(const acoss_crp_params* P) {
@@ -985,6 +988,118 @@ extern "C" int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t
   launch_dp(align, gamma_open == gamma_ext, 1, M, V.maskT, 0, V.ld, V.d_dims, gamma_open, gamma_ext,
             reinterpret_cast<float4*>(V.region[0]), 0, score_out, s);
   ACOSS_LAUNCH_CHECK();
+  return matrix_finish(V, s);
+}
+
+// Cross-recurrence quantification. The line measures come from one walk over the mask words
+// (launch_rqa), Smax from the shipped Qmax DP at gamma_open = gamma_ext = +inf, where the miss
+// branch max(mx - gamma, 0) is 0: launch_dp(align 0, eqg, ..., inf, inf), its general kernel.
+namespace {
+
+int check_rqa_args(const char* entry, int32_t lmin, int32_t hist_cap, const int32_t* hist_out) {
+  if (lmin < 1) {
+    set_error("%s: lmin %d below 1", entry, lmin);
+    return ACOSS_E_ARG;
+  }
+  if (hist_cap < 0 || (hist_out && hist_cap == 0)) {
+    set_error("%s: hist_out needs a positive hist_cap, not %d", entry, hist_cap);
+    return ACOSS_E_ARG;
+  }
+  return ACOSS_OK;
+}
+
+int check_rqa_line(int longest) {
+  if (longest <= kRqaMaxLine) return ACOSS_OK;
+  set_error("a diagonal line may have %d cells, above the %d the LDS histogram takes", longest, kRqaMaxLine);
+  return ACOSS_E_SHAPE;
+}
+
+}  // namespace
+
+extern "C" int acoss_crp_rqa(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                             int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                             int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                             int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
+  clear_error();
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const bool lines = counts_out || lmax_out || stats_out || hist_out;
+  void* rb = nullptr;  // band-boundary records of the line walk, rstride per pair
+  int64_t rstride = 0;
+  return crp_batches(
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out,
+      [&] {
+        if (int rc = check_rqa_args("acoss_crp_rqa", lmin, hist_cap, hist_out)) return rc;
+        return lines ? check_rqa_line(stacked_len(max_len, params->m, params->tau)) : ACOSS_OK;
+      },
+      [&](const CrpPlan& C, int64_t& nbd) {
+        rstride = rqa_bnd_records(C.L, C.ld);
+        rb = workspace(SLOT_RQA, kRqaRecBytes * (size_t)rstride * (size_t)nbd);
+        return rb ? ACOSS_OK : ACOSS_E_HIP;
+      },
+      [&](const CrpPlan& C, int64_t base, int nb) {
+        if (lines) {
+          prof_begin(PH_RQA, s);
+          launch_rqa(nb, C.L, C.L + 1, C.mask, C.mask_stride, C.ld, C.dims, lmin, rb, rstride,
+                     counts_out ? counts_out + 4 * base : nullptr, lmax_out ? lmax_out + base : nullptr,
+                     stats_out ? stats_out + 4 * base : nullptr, hist_cap,
+                     hist_out ? hist_out + (size_t)hist_cap * (size_t)base : nullptr, s);
+          ACOSS_LAUNCH_CHECK();
+          prof_end(PH_RQA, s);
+        }
+        if (smax_out) {
+          prof_begin(PH_DP_QMAX, s);
+          launch_dp(0, true, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, __builtin_inff(), __builtin_inff(), C.bnd,
+                    C.bnd_stride, smax_out + base, s);
+          ACOSS_LAUNCH_CHECK();
+          prof_end(PH_DP_QMAX, s);
+        }
+        return ACOSS_OK;
+      });
+}
+
+extern "C" int acoss_rqa_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t lmin, int64_t* counts_out,
+                             int32_t* lmax_out, double* stats_out, float* smax_out, int32_t hist_cap,
+                             int32_t* hist_out, void* hip_stream) {
+  clear_error();
+  if (M < 0 || N < 0) {
+    set_error("bad arguments to acoss_rqa_crp");
+    return ACOSS_E_ARG;
+  }
+  int rc;
+  if ((rc = check_rqa_args("acoss_rqa_crp", lmin, hist_cap, hist_out))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const bool lines = counts_out || lmax_out || stats_out || hist_out;
+  if (M == 0 || N == 0) {  // no cell, no line: every result is 0
+    if (counts_out) ACOSS_HIP_CHECK(hipMemsetAsync(counts_out, 0, 4 * sizeof(int64_t), s));
+    if (lmax_out) ACOSS_HIP_CHECK(hipMemsetAsync(lmax_out, 0, sizeof(int32_t), s));
+    if (stats_out) ACOSS_HIP_CHECK(hipMemsetAsync(stats_out, 0, 4 * sizeof(double), s));
+    if (smax_out) ACOSS_HIP_CHECK(hipMemsetAsync(smax_out, 0, sizeof(float), s));
+    if (hist_out) ACOSS_HIP_CHECK(hipMemsetAsync(hist_out, 0, sizeof(int32_t) * (size_t)hist_cap, s));
+    ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+    return ACOSS_OK;
+  }
+  if (lines) {
+    if ((rc = check_rqa_line(M < N ? M : N))) return rc;
+    if ((int64_t)M * N > (int64_t)INT32_MAX) {  // a bin of H is an int32, and a bin can hold half the cells' count
+      set_error("matrix %d x %d has more than 2^31 - 1 cells: a histogram bin is an int32", M, N);
+      return ACOSS_E_SHAPE;
+    }
+  }
+  MatrixView V;
+  const int ld = matrix_pitch(N);
+  if ((rc = pack_matrix(SLOT_RQA_CRP, crp, M, N, kRqaRecBytes * (size_t)rqa_bnd_records(M, ld),
+                        sizeof(float4) * (size_t)((M + 2047) / 2048) * ld, s, V)))
+    return rc;
+  if (lines) {
+    launch_rqa(1, M, (M < N ? M : N) + 1, V.maskT, 0, ld, V.d_dims, lmin, V.region[0], 0, counts_out, lmax_out,
+               stats_out, hist_cap, hist_out, s);
+    ACOSS_LAUNCH_CHECK();
+  }
+  if (smax_out) {
+    launch_dp(0, true, 1, M, V.maskT, 0, ld, V.d_dims, __builtin_inff(), __builtin_inff(),
+              reinterpret_cast<float4*>(V.region[1]), 0, smax_out, s);
+    ACOSS_LAUNCH_CHECK();
+  }
   return matrix_finish(V, s);
 }
 

@@ -13,6 +13,7 @@
 //      DpLanePk  chen17 at gamma = K/2 in packed 16-bit integers, two rows per instruction
 //      DpLaneT   either alignment with the cell where each path began carried beside every score
 //      DpLaneD   either alignment's scores that leave a 2-bit predecessor code per cell in a plane
+//      DpLaneR   no alignment: the length of the diagonal run ending on each cell, counted where it ends
 //  * an edge policy: what is above the chain's first lane and below its last one.
 //      Band       the band above / below, through HBM records
 //      GroupEdge  nothing above, nothing kept: several short pairs per wave, one band each
@@ -27,7 +28,9 @@
 //                            and acoss_crp_locate_dmax / acoss_locate_crp_dmax (ALIGN 1)
 //  k_crp_dp_dir<ALIGN, EQG, R>    DpLaneD in bands, and k_crp_backtrack / k_crp_backtrack_dmax, the walk
 //                            back over its plane, for acoss_crp_path / acoss_path_crp and their _dmax twins
-// launch_dp, launch_trace and launch_dir choose among them.
+//  k_crp_rqa<R>              DpLaneR in bands and the fold of its line histogram, for acoss_crp_rqa /
+//                            acoss_rqa_crp
+// launch_dp, launch_trace, launch_dir and launch_rqa choose among them.
 #include <cstdlib>
 #include <type_traits>
 
@@ -1020,6 +1023,201 @@ __global__ __launch_bounds__(64) void k_crp_backtrack_dmax(const uint8_t* __rest
 }
 
 // --------------------------------------------------------------------------------------
+// k_crp_rqa<R>: cross-recurrence quantification of a pair (the definition: include/acoss_hip.h,
+// acoss_crp_rqa): the histogram H of its diagonal lines, folded by the same wave into n_rec, the
+// line counts, lmax and RR, DET, LMEAN, ENTR. One wave per pair in bands, as k_crp_dp.
+//  * DpLaneR keeps L[r][c], the length of the diagonal run that ends on (r, c): L[r-1][c-1] + 1 on
+//    a hit, else 0. It depends on column c-1 only; what goes down a lane is the last row's L and the
+//    CRP bits of the last three rows. All M' rows and N' columns count (no "rows and columns 0 and 1
+//    hold 0" here): the fetch masks the words to the matrix and nothing else.
+//  * a run is counted once, where it ends: at a miss inside the matrix whose up-left neighbour is
+//    set (the run's length is that neighbour's L), and at once at a hit in the last row or the last
+//    column (its own L): no virtual row below a full last band, no column N'.
+//  * nearly all runs are short, so the two hottest bins never see an atomic: with e_k = "bit r is
+//    C[r-k][c-k]" (the words of columns c-1, c-2, c-3 shifted by 1, 2, 3 rows, the rows from above
+//    spliced in), a run of length 1 ends where e_1 & ~e_2, one of length 2 where e_1 & e_2 & ~e_3
+//    (at an edge hit: ~e_1, and e_1 & ~e_2): two popcounts per column into lane registers, summed
+//    over the wave once. Only runs of 3 cells and more go to the pair's LDS histogram (dynamic,
+//    nbins counters), by an atomic add under a branch most steps skip.
+//  * n_rec is the popcount of the masked words.
+// The fold: lane t takes the bins t, t + 64, ... in ascending order, integers exactly; ENTR in
+// float64, -p ln p summed per lane in that order and then over the lanes by the xor butterfly
+// (32, 16, ..., 1): one fixed order.
+// --------------------------------------------------------------------------------------
+struct DpAboveR {  // what lane l-1 (or the band above) hands down for one column
+  uint32_t l;      // L of its last row
+  uint32_t b;      // bit0 = C[row R-3], bit1 = C[row R-2], bit2 = C[row R-1]
+};
+
+template <int R>
+struct DpLaneR {
+  static constexpr int kRows = R;
+  using Above = DpAboveR;
+  using Rec = uint2;  // l, b
+  using Col = uint32_t[R];  // one column: the run length that ends on each of this lane's rows
+  static __device__ __forceinline__ Above shfl_up(const Above& a) {
+    return Above{(uint32_t)__shfl_up((int)a.l, 1), (uint32_t)__shfl_up((int)a.b, 1)};
+  }
+  static __device__ __forceinline__ Above from_rec(const Rec& v) { return Above{v.x, v.y}; }
+  static __device__ __forceinline__ Rec to_rec(const Above& o) { return make_uint2(o.l, o.b); }
+
+  int Np;
+  uint32_t rin;         // bit r: global row < Mp
+  uint32_t lastrow;     // bit r: global row == Mp - 1
+  uint32_t w1, w2, w3;  // CRP words of columns c-1, c-2, c-3 (bit r = row r)
+  DpAboveR h1, h2, h3;  // from above for the same columns
+  uint32_t n_rec, n1, n2;  // set cells, runs of length 1 and of length 2 that this lane saw end
+  uint32_t* hist;       // the pair's LDS histogram and its last bin
+  uint32_t maxbin;
+
+  __device__ __forceinline__ DpAboveR step(Col& qn, const Col& q1, const Col&, uint32_t w0, const DpAboveR& h0, int c) {
+    // bit r of e_k: C[r-k][c-k]; a neighbour outside the matrix reads 0 (the fetch, the top edge)
+    const uint32_t e1 = (w1 << 1) | (h1.b >> 2);
+    const uint32_t e2 = (w2 << 2) | (h2.b >> 1);
+    const uint32_t e3 = (w3 << 3) | h3.b;
+    const bool incol = c >= 0 && c < Np;
+    const uint32_t ends = e1 & ~w0 & (incol ? rin : 0u);       // misses that end a run
+    const uint32_t edge = w0 & (c == Np - 1 ? rin : lastrow);  // hits no cell can follow
+    n_rec += __builtin_popcount(w0);
+    n1 += __builtin_popcount((ends & ~e2) | (edge & ~e1));
+    n2 += __builtin_popcount((ends & e2 & ~e3) | (edge & e1 & ~e2));
+    const uint32_t lng = (ends & e2 & e3) | (edge & e1 & e2);  // runs of 3 cells and more
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint32_t prev = r >= 1 ? q1[r - 1] : h1.l;
+      qn[r] = ((w0 >> r) & 1u) ? prev + 1u : 0u;
+    }
+    if (lng) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if ((lng >> r) & 1u) {
+          const uint32_t prev = r >= 1 ? q1[r - 1] : h1.l;
+          atomicAdd(&hist[min(max(qn[r], prev), maxbin)], 1u);  // prev at a miss, prev + 1 at an edge hit
+        }
+      }
+    }
+    DpAboveR out;
+    out.l = qn[R - 1];
+    out.b = (w0 >> (R - 3)) & 7u;
+    h3 = h2;
+    h2 = h1;
+    h1 = h0;
+    w3 = w2;
+    w2 = w1;
+    w1 = w0;
+    return out;
+  }
+};
+
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {  // the total in every lane
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o);
+  return v;
+}
+
+// bnd: ceil(L / 2048) * ld records per pair (only CRPs of more than one band touch them); dynamic
+// LDS: nbins counters, nbins - 1 >= min(M', N') of every pair. counts (4 per pair: n_rec, n_lines,
+// n_lines_min, n_pts_min), lmax, stats (4 per pair: RR, DET, LMEAN, ENTR) and hist (hist_cap per
+// pair) may each be NULL.
+template <int R>
+__global__ __launch_bounds__(64) void k_crp_rqa(const uint32_t* __restrict__ maskT, int64_t mask_stride, int ld,
+                                                const int2* __restrict__ dims, int lmin, int nbins,
+                                                uint2* __restrict__ bnd, int64_t bnd_stride,
+                                                int64_t* __restrict__ counts, int32_t* __restrict__ lmax_out,
+                                                double* __restrict__ stats, int hist_cap,
+                                                int32_t* __restrict__ hist_out) {
+  using Lane = DpLaneR<R>;
+  extern __shared__ uint32_t s_hist[];
+  const int p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int2 dm = dims[p];
+  const int Mp = dm.x, Np = dm.y;
+  for (int t = lane; t < nbins; t += 64) s_hist[t] = 0u;
+  __syncthreads();
+  const int nbands = (Mp > 0 && Np > 0) ? (Mp + 64 * R - 1) / (64 * R) : 0;
+  Lane L;
+  L.Np = Np;
+  L.n_rec = L.n1 = L.n2 = 0u;
+  L.hist = s_hist;
+  L.maxbin = (uint32_t)(nbins - 1);
+  for (int band = 0; band < nbands; ++band) {
+    const Band<Lane> B(p, band, nbands, lane, maskT, mask_stride, ld, bnd, bnd_stride);
+    const int left = Mp - B.row0;  // rows of the matrix from this lane's first one on
+    const int own = left < 0 ? 0 : (left < R ? left : R);  // how many of them are this lane's
+    const uint32_t rin = L.rin = own >= 32 ? 0xffffffffu : (1u << own) - 1u;
+    L.lastrow = (left >= 1 && left <= R) ? 1u << (left - 1) : 0u;
+    L.w3 = 0u;
+    L.h3 = DpAboveR{};
+    dp_walk(L, B, lane, Np + 63, [&](int c) -> uint32_t {
+      if (!(rin != 0u && c >= 0 && c < Np)) return 0u;
+      return (B.mrow[c] >> B.sh) & rin;
+    });
+    __threadfence_block();
+    __syncthreads();
+  }
+  const int64_t n_rec = wave_sum_i64((int64_t)L.n_rec);
+  const int64_t h1 = wave_sum_i64((int64_t)L.n1), h2 = wave_sum_i64((int64_t)L.n2);
+  if (lane == 0) {
+    if (nbins > 1) s_hist[1] += (uint32_t)h1;
+    if (nbins > 2) s_hist[2] += (uint32_t)h2;
+  }
+  __syncthreads();
+  const int lim = min(min(Mp, Np), nbins - 1);  // the longest line the pair can hold
+  int64_t nl = 0, nlm = 0, npm = 0;
+  int lm = 0;
+  for (int l = 1 + lane; l <= lim; l += 64) {
+    const int64_t h = (int64_t)s_hist[l];
+    nl += h;
+    if (l >= lmin) {
+      nlm += h;
+      npm += h * l;
+    }
+    if (h > 0) lm = l;
+  }
+  nl = wave_sum_i64(nl);
+  nlm = wave_sum_i64(nlm);
+  npm = wave_sum_i64(npm);
+  lm = (int)wave_max_u32((unsigned)lm);
+  if (hist_out) {
+    int32_t* const ho = hist_out + (size_t)p * hist_cap;
+    for (int l = lane; l < hist_cap; l += 64) ho[l] = (l >= 1 && l <= lim) ? (int32_t)s_hist[l] : 0;
+  }
+  if (stats) {  // wave-uniform
+    double e = 0.0;
+    if (nlm > 0) {
+      const double tot = (double)nlm;
+      for (int l = 1 + lane; l <= lim; l += 64) {
+        const uint32_t h = s_hist[l];
+        if (l >= lmin && h > 0u) {
+          const double pl = (double)h / tot;
+          e -= pl * log(pl);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+    }
+    if (lane == 0) {
+      double* st = stats + 4 * (size_t)p;
+      const double cells = (double)Mp * (double)Np;
+      st[0] = cells > 0.0 ? (double)n_rec / cells : 0.0;
+      st[1] = n_rec > 0 ? (double)npm / (double)n_rec : 0.0;
+      st[2] = nlm > 0 ? (double)npm / (double)nlm : 0.0;
+      st[3] = e;
+    }
+  }
+  if (lane == 0) {
+    if (counts) {
+      int64_t* ct = counts + 4 * (size_t)p;
+      ct[0] = n_rec;
+      ct[1] = nl;
+      ct[2] = nlm;
+      ct[3] = npm;
+    }
+    if (lmax_out) lmax_out[p] = lm;
+  }
+}
+
+// --------------------------------------------------------------------------------------
 // Which kernel runs
 // --------------------------------------------------------------------------------------
 namespace {
@@ -1151,6 +1349,24 @@ void launch_backtrack(int align, int nb, const uint8_t* plane, int64_t pstride, 
   else
     hipLaunchKernelGGL(k_crp_backtrack_dmax, dim3(nb), dim3(64), 0, s, plane, pstride, maskT, mstride, ld, dims, endkey,
                        path_cap, seg, len, path);
+}
+
+int64_t rqa_bnd_records(int L, int ld) { return (int64_t)((L + 2047) / 2048) * ld; }
+
+void launch_rqa(int nb, int L, int nbins, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, int lmin,
+                void* bnd, int64_t bstride, int64_t* counts, int32_t* lmax, double* stats, int hist_cap, int32_t* hist,
+                hipStream_t s) {
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(64), sizeof(uint32_t) * (size_t)nbins, s, maskT, mstride, ld, dims, lmin,
+                       nbins, static_cast<uint2*>(bnd), bstride, counts, lmax, stats, hist_cap, hist);
+  };
+  // rows per lane as launch_dp's: one band up to 2048 rows
+  if (L <= 512)
+    launch(k_crp_rqa<8>);
+  else if (L <= 1024)
+    launch(k_crp_rqa<16>);
+  else
+    launch(k_crp_rqa<32>);
 }
 
 }  // namespace acoss

@@ -65,6 +65,19 @@ void launch_backtrack(int align, int nb, const uint8_t* plane, int64_t pstride, 
                       int ld, const int2* dims, const uint32_t* endkey, int path_cap, int32_t* seg, int32_t* len,
                       int32_t* path, hipStream_t s);
 
+// Cross-recurrence quantification (k_crp_rqa; the definition: include/acoss_hip.h, acoss_crp_rqa):
+// per pair the diagonal-line histogram of its CRP words, folded into counts[p] = (n_rec, n_lines,
+// n_lines_min, n_pts_min), lmax[p], stats[p] = (RR, DET, LMEAN, ENTR) and hist[p][l] = H[l] for
+// l < hist_cap; each of the four may be NULL. nbins: counters of the per-pair LDS histogram,
+// nbins - 1 >= min(M', N') of every pair and <= kRqaMaxLine; bnd: rqa_bnd_records(L, ld) records of
+// kRqaRecBytes per pair.
+constexpr int kRqaMaxLine = 16383;  // the longest line the LDS histogram takes: 16,384 bins, 64 KiB
+constexpr size_t kRqaRecBytes = 8;
+int64_t rqa_bnd_records(int L, int ld);
+void launch_rqa(int nb, int L, int nbins, const uint32_t* maskT, int64_t mstride, int ld, const int2* dims, int lmin,
+                void* bnd, int64_t bstride, int64_t* counts, int32_t* lmax, double* stats, int hist_cap, int32_t* hist,
+                hipStream_t s);
+
 // The most cells a dmax (chen17) path of an M x N matrix can have: floor(2 (M + N) / 3) - 2 for
 // M, N >= 3, none below. Proof. Call the cells with a DP value the chain X_0 .. X_n (X_n the end
 // cell); all lie in rows and columns >= 2, so i + j is at least 4 at X_0 and at most M + N - 2 at

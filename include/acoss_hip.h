@@ -184,6 +184,47 @@ int acoss_crp_path_dmax(const float* feats, const int64_t* track_off, const int3
 int acoss_path_crp_dmax(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext, float* score_out,
                         int32_t* seg_out, int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream);
 
+/* Cross-recurrence quantification of every pair's CRP (Serra, Serra and Andrzejak 2009 define Lmax,
+ * Smax and Qmax on the cross-recurrence plot; the line measures are the standard CRQA ones, Marwan
+ * et al. 2007). No counterpart call in the reference, which keeps only Qmax. The CRP is the one
+ * acoss_crp_align computes (same kernels, same workspace); the line measures come from one more
+ * walk over its words (crp_dp.hip k_crp_rqa).
+ *
+ * The definition. C is the pair's binary M x N matrix; all M rows and N columns count (the "rows
+ * and columns 0 and 1 hold 0" convention belongs to the Q / S score matrices only).
+ *   lines: a diagonal line is a maximal run of set cells (i, j), (i+1, j+1), ..., bounded on each
+ *     side by an unset cell or the matrix edge. H[l] = the number of lines of length l,
+ *     1 <= l <= min(M, N). lmin >= 1 is the shortest line the "min" measures take (2 is the usual
+ *     CRQA setting).
+ *   integers: n_rec = set cells (= sum l H[l]); n_lines = sum H[l]; n_lines_min = sum_{l >= lmin}
+ *     H[l]; n_pts_min = sum_{l >= lmin} l H[l] (int64); lmax = the largest l with H[l] > 0 (int32, 0
+ *     for a matrix without a set cell).
+ *   float64, each of the first three ONE IEEE division of two exactly representable integers:
+ *     RR = n_rec / (M N); DET = n_pts_min / n_rec (0 when n_rec = 0); LMEAN = n_pts_min /
+ *     n_lines_min (0 without such lines); ENTR = - sum_{l >= lmin, H[l] > 0} p(l) ln p(l) with
+ *     p(l) = H[l] / n_lines_min (0 when n_lines_min = 0), float64 log, a fixed summation order.
+ *   Smax: the Q recurrence without its penalties: cells with i < 2 or j < 2 hold 0; on a hit
+ *     S = max(S[i-1, j-1], S[i-2, j-1], S[i-1, j-2]) + 1, on a miss S = 0; Smax = max S, float32.
+ *     It is acoss_crp_align's Qmax DP at gamma_open = gamma_ext = +inf, and computed by it.
+ * counts_out: int64[n_pairs][4] = n_rec, n_lines, n_lines_min, n_pts_min; lmax_out: int32[n_pairs];
+ * stats_out: double[n_pairs][4] = RR, DET, LMEAN, ENTR; smax_out: float[n_pairs]; oti_out:
+ * int32[n_pairs]; hist_out: int32[n_pairs][hist_cap], hist_out[p][l] = H[l] for 1 <= l < hist_cap
+ * and 0 at l = 0 and beyond min(M, N) (a hist_cap below lmax cuts the copy, not the counts). Every
+ * output may be NULL and is then not computed; smax_out NULL skips the S pass. lmin < 1 returns
+ * ACOSS_E_ARG, as does hist_out with hist_cap < 1. The line histogram of a pair lives in LDS and
+ * takes lines of at most 16,383 cells (16,384 bins, 64 KiB): a stacked length of max_len above that
+ * returns ACOSS_E_SHAPE when a line measure is asked for. */
+int acoss_crp_rqa(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                  int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                  int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                  int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream);
+/* the same on a given binary matrix (mirrors acoss_align_crp, non-binary input refused alike):
+ * counts_out int64[4], lmax_out int32[1], stats_out double[4], smax_out float[1], hist_out
+ * int32[hist_cap]. An empty matrix is answered with zeros. min(M, N) above 16,383, or more than
+ * 2^31 - 1 cells (a bin is an int32), returns ACOSS_E_SHAPE when a line measure is asked for. */
+int acoss_rqa_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t lmin, int64_t* counts_out, int32_t* lmax_out,
+                  double* stats_out, float* smax_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream);
+
 /* acoss smith_waterman_constrained (A8, acoss/algorithms/utils/alignment_tools.py:25-46) on
  * a batch of binary matrices: matrix b is (rows[b] x cols[b]) uint8 at byte offset off[b]
  * of `mats`. score_out: double[n_mats]. Bit-exact float64 (same evaluation order). */
