@@ -76,6 +76,8 @@ SIGNATURES = {
     "acoss_snf_left_rows": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, ctypes.c_double, _vp, _i32, _vp],
     "acoss_simple_mp": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
     "acoss_simple_profile": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "acoss_simple_self_profile": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
+                                  _vp],
     "acoss_median_downsample": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "acoss_simple_features": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp],
     "acoss_earlyfusion": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, ctypes.c_double,
@@ -820,6 +822,74 @@ def simple_profile(feats, pairs, sslen=10, apply_oti=True):
             raise ValueError("SiMPle features are (12, n) blocks")
     flat, off, _, cols, _, _ = _pack_mats(mats, torch.float64)
     return simple_profile_packed(flat, off, cols, pairs, sslen, apply_oti)
+
+
+def _self_excl(sslen, excl):
+    """The exclusion half-width of a self-join: sslen // 2 unless given; never negative."""
+    excl = int(sslen) // 2 if excl is None else int(excl)
+    if excl < 0:
+        raise ValueError("excl must be >= 0, got %d" % excl)
+    return excl
+
+
+def simple_self_profile_offsets(track_len, tracks, sslen):
+    """Where each listed track's self-profile starts in the ragged output of simple_self_profile
+    (host only, pure numpy): int64 (n_sel + 1,), entry e's rows at [off[e], off[e + 1]), as many as
+    the track has length-sslen subsequences, max(len[tracks[e]] - sslen + 1, 0)."""
+    lens = np.asarray(track_len, np.int64).reshape(-1)
+    tracks = np.asarray(tracks, np.int64).reshape(-1)
+    if len(tracks) and (int(tracks.min()) < 0 or int(tracks.max()) >= len(lens)):
+        raise ValueError("track indices must lie in [0, %d)" % len(lens))
+    off = np.zeros(len(tracks) + 1, np.int64)
+    np.cumsum(np.maximum(lens[tracks] - int(sslen) + 1, 0), out=off[1:])
+    return off
+
+
+def simple_self_profile_packed(flat, track_off, track_len, tracks, sslen=10, excl=None):
+    """The SiMPle self-join per listed track (acoss_simple_self_profile) over packed (12 x n_t)
+    float64 blocks, as simple_mp_packed takes them: the matrix profile of a track against itself
+    without the matches within excl subsequences of the row itself (excl=None: sslen // 2).
+    Returns a dict of device tensors: off i64 (n_sel + 1,) (simple_self_profile_offsets), mp f64
+    and mpi i32 (off[-1],) ragged by off (row i of entry e: its distance to the nearest admissible
+    subsequence of the same track and that subsequence's index; NaN and -1 where there is none),
+    motif i32 (n_sel, 2) (the row of the smallest mp and its mpi: the repeated section) and discord
+    i32 (n_sel,) (the row of the largest mp); -1 for a track without a row that is not NaN."""
+    excl = _self_excl(sslen, excl)
+    torch = _torch()
+    lib = load_library()
+    lens = np.asarray(track_len.cpu() if isinstance(track_len, torch.Tensor) else track_len, np.int64)
+    host_tracks = np.asarray(tracks.cpu() if isinstance(tracks, torch.Tensor) else tracks, np.int64).reshape(-1)
+    off = simple_self_profile_offsets(lens, host_tracks, sslen)
+    n_sel, total = len(host_tracks), int(off[-1])
+    mp = torch.empty(total, dtype=torch.float64, device="cuda")
+    mpi = torch.empty(total, dtype=torch.int32, device="cuda")
+    motif = torch.empty((n_sel, 2), dtype=torch.int32, device="cuda")
+    discord = torch.empty(n_sel, dtype=torch.int32, device="cuda")
+    flat_d = _dev(flat, torch.float64)
+    off_d = _dev(track_off, torch.int64)
+    len_d = _dev(lens.astype(np.int32), torch.int32)
+    trk_d = _dev(host_tracks.astype(np.int32), torch.int32)
+    poff_d = _dev(off, torch.int64)
+    rc = lib.acoss_simple_self_profile(_ptr(flat_d), _ptr(off_d), _ptr(len_d), len(lens), int(lens.max(initial=0)),
+                                       _ptr(trk_d), n_sel, int(sslen), excl, _ptr(poff_d), total, _ptr(mp), _ptr(mpi),
+                                       _ptr(motif), _ptr(discord), _stream())
+    _check(rc, "acoss_simple_self_profile")
+    return {"off": poff_d, "mp": mp, "mpi": mpi, "motif": motif, "discord": discord}
+
+
+def simple_self_profile(feats, tracks=None, sslen=10, excl=None):
+    """simple_self_profile_packed for a list of (12, n) float64 arrays, as simple_mp takes them;
+    tracks=None profiles every one of them."""
+    excl = _self_excl(sslen, excl)
+    torch = _torch()
+    mats = [np.asarray(f) if not isinstance(f, torch.Tensor) else f for f in feats]
+    for f in mats:
+        if f.shape[0] != 12:
+            raise ValueError("SiMPle features are (12, n) blocks")
+    flat, off, _, cols, _, _ = _pack_mats(mats, torch.float64)
+    if tracks is None:
+        tracks = np.arange(len(mats), dtype=np.int32)
+    return simple_self_profile_packed(flat, off, cols, tracks, sslen, excl)
 
 
 def median_downsample(feats, track_off, track_len, factor=40):

@@ -9,6 +9,9 @@ means, Hann smoothing, column L2 norm; the reference recomputes them for every p
 call (simple.hip: Simple.oti + matrix profile + median). Ds['main'][i, j] = -median(MP).
 `profile(idxs)` returns the matrix profile itself and its index per pair (acoss_simple_profile):
 which part of the reference each part of the query is nearest to.
+`self_profile(tracks)` is the paper's other join, a song against itself without the trivial
+matches (acoss_simple_self_profile): its repeated section (motif) and its most unusual passage
+(discord).
 """
 import argparse
 
@@ -105,6 +108,35 @@ class Simple(CoverAlgorithm):
                                                np.repeat(self._n_frames[idxs[:, 0]], rows))
         r["reference_frames"] = subsequence_frames(r["mpi"], self.SSLEN, self.WIN, self.SKIP,
                                                    np.repeat(self._n_frames[idxs[:, 1]], rows))
+        return r
+
+    def self_profile(self, tracks=None, excl=None):
+        """The self-join of every song of `tracks` (None: every song): its matrix profile against
+        itself without the trivial matches, the rows within `excl` subsequences of the row itself
+        (None: SSLEN // 2), its motif and its discord (acoss_simple_self_profile). A dict of host
+        arrays: 'off' (n + 1,) int64, 'mp' (total,) float64 and 'mpi' (total,) int32 (row i of
+        entry e at off[e] + i: the distance of subsequence i to its nearest admissible subsequence
+        of the same song and that subsequence's first column; NaN and -1 where there is none),
+        'motif' (n, 2) int32 (the row of the smallest mp and its mpi: the song's repeated section)
+        and 'discord' (n,) int32 (the row of the largest mp: its most unusual passage), -1 where a
+        song has no row; and the half-open ranges in frames of `chroma_type` before the window
+        means (engine.subsequence_frames, (-1, -1) where an index is -1): 'frames' and
+        'match_frames' (total, 2) int64 of row i and of mpi, 'motif_frames' (n, 2, 2) and
+        'discord_frames' (n, 2). Not collective: a rank profiles the songs it is given."""
+        self.prepare()
+        tracks = np.arange(self.N, dtype=np.int32) if tracks is None else np.asarray(tracks, np.int32).reshape(-1)
+        out, off, T = self._packed
+        r = {k: v.cpu().numpy()
+             for k, v in _lib.simple_self_profile_packed(out, off, T, tracks, self.SSLEN, excl).items()}
+        rows = np.diff(r["off"])
+        i = np.arange(r["off"][-1]) - np.repeat(r["off"][:-1], rows)
+        nf = self._n_frames[tracks]
+        nrow = np.repeat(nf, rows)
+        r["frames"] = subsequence_frames(i, self.SSLEN, self.WIN, self.SKIP, nrow)
+        r["match_frames"] = subsequence_frames(r["mpi"], self.SSLEN, self.WIN, self.SKIP, nrow)
+        r["motif_frames"] = subsequence_frames(r["motif"].reshape(-1), self.SSLEN, self.WIN, self.SKIP,
+                                               np.repeat(nf, 2)).reshape(-1, 2, 2)
+        r["discord_frames"] = subsequence_frames(r["discord"], self.SSLEN, self.WIN, self.SKIP, nf)
         return r
 
     def _device_scores(self, idxs):

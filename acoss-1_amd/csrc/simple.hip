@@ -35,6 +35,11 @@
 // column attaining each (the profile index): the PROF = 1 instantiations of k_simple_mfma (L = 10)
 // and k_simple_pair (other L) walk a pair twice, the second time comparing every distance with its
 // row's minimum. The PROF = 0 instantiations are the score kernels, instruction for instruction.
+//
+// acoss_simple_self_profile is the paper's other join, a track against itself: the SELF = 1
+// instantiations of the same two kernels leave out the trivial matches, the cells within excl of
+// the main diagonal, and form neither OTI nor median; k_simple_motif then reduces each profile to
+// its motif (smallest entry) and discord (largest entry).
 #include "common.hpp"
 
 namespace acoss {
@@ -184,7 +189,7 @@ __global__ void k_simple_track(const double* __restrict__ feats, const int64_t* 
 
 // What the profile instantiations of the pair kernels write besides the score: the profile and its
 // index, ragged by off (acoss_simple_profile). The score instantiations carry an empty struct.
-template <int PROF>
+template <int PROF, int SELF = 0>
 struct ProfOut {};
 template <>
 struct ProfOut<1> {
@@ -192,18 +197,31 @@ struct ProfOut<1> {
   double* mp;
   int32_t* mpi;
 };
+// SELF = 1 (acoss_simple_self_profile): the pairs are (t, t) and the cells within excl of the main
+// diagonal, the trivial matches, take no part: |i - j| <= excl offers neither a minimum nor a
+// column. No OTI and no median are formed (score and oti_out are not touched).
+template <>
+struct ProfOut<1, 1> {
+  const int64_t* off;
+  double* mp;
+  int32_t* mpi;
+  int excl;  // exclusion half-width, >= 0
+};
 
 // Generic sslen (1..16): one thread per diagonal, L-deep shift register of G.
 // PROF = 1 also returns the row minima and their columns: the diagonal walk runs a second time
 // (mode 1) and every distance equal to its row's minimum offers its column to an LDS atomicMin on
 // mpi_s[row] (the same IEEE operations in the same order as in mode 0, so equality is exact).
-template <int PROF>
+// SELF = 1: a thread's diagonal is inside the exclusion band or outside it for its whole length, so
+// the band's diagonals are skipped whole.
+template <int PROF, int SELF = 0>
 __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ feats, const int64_t* __restrict__ off,
                                                      const int32_t* __restrict__ len, const int32_t* __restrict__ pairs,
                                                      const double* __restrict__ prof, const double* __restrict__ wnorm,
                                                      const int64_t* __restrict__ toff, int L, int apply_oti,
                                                      double* __restrict__ score,
-                                                     int32_t* __restrict__ oti_out, ProfOut<PROF> po) {
+                                                     int32_t* __restrict__ oti_out, ProfOut<PROF, SELF> po) {
+  static_assert(!SELF || PROF, "the self-join returns a profile");
   __shared__ double sa[kMaxLen];
   __shared__ double sb[kMaxLen];
   __shared__ unsigned long long mpk[kMaxLen];
@@ -217,13 +235,13 @@ __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ 
   const double* A = feats + off[ta];
   const double* B = feats + off[tb];
   const int P = na - L + 1, Q = nb - L + 1;
-  if (t == 0) {
+  if (!SELF && t == 0) {
     const int best = simple_oti_index(prof + ta * 12, prof + tb * 12);
     s_k = apply_oti ? best : 0;
     if (oti_out) oti_out[p] = best;
   }
   if (P <= 0 || Q <= 0) {
-    if (t == 0) score[p] = __builtin_nan("");
+    if (!SELF && t == 0) score[p] = __builtin_nan("");
     if constexpr (PROF)
       for (int i = t; i < P; i += 256) {  // rows without a distance: the untouched key's NaN, no column
         po.mp[po.off[p] + i] = dkey_inv(~0ull);
@@ -237,7 +255,7 @@ __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ 
     if constexpr (PROF) mpi_s[i] = INT32_MAX;
   }
   __syncthreads();
-  const int k = s_k;
+  const int k = SELF ? 0 : s_k;
   int rowA[12];  // reference bin j pairs with query bin (j + k) mod 12
 #pragma unroll
   for (int c = 0; c < 12; ++c) rowA[c] = ((c + k) % 12) * na;
@@ -250,6 +268,9 @@ __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ 
   do {
   for (int dg = t; dg < P + Q - 1; dg += 256) {
     const int o = dg - (P - 1);  // j - i
+    if constexpr (SELF) {
+      if (abs(o) <= po.excl) continue;  // a trivial match, every cell of it
+    }
     const int r0 = o < 0 ? -o : 0;
     const int r1 = min(P - 1, Q - 1 - o);  // last row on this diagonal
     double buf[kMaxL];
@@ -287,6 +308,7 @@ __global__ __launch_bounds__(256) void k_simple_pair(const double* __restrict__ 
       po.mp[po.off[p] + i] = dkey_inv(mpk[i]);
       po.mpi[po.off[p] + i] = mpi_s[i] == INT32_MAX ? -1 : mpi_s[i];
     }
+  if constexpr (SELF) return;
   // median: the order statistics P/2 (and P/2 - 1 for even P) by exact rank counting
   const int k_hi = P / 2, k_lo = (P % 2) ? P / 2 : P / 2 - 1;
   for (int e = t; e < P; e += 256) {
@@ -605,13 +627,32 @@ typedef double f64x4m __attribute__((ext_vector_type(4)));
 // atomicMin(&mpi[row]). Lanes own increasing diagonals, so of a wave's matching lanes the lowest,
 // and its lowest k, holds the wave's smallest column: one ballot per step, at most one atomic per
 // row and wave group, however many distances tie.
-template <int PROF>
+//
+// SELF = 1 (the self-join, pairs (t, t)): a lane's kKM diagonals are inside the exclusion band
+// |j - i| <= excl or outside it for a group's whole walk, so the two memberships are formed once per
+// group (the compiler keeps each as a lane mask in an SGPR pair: no VGPR) and a distance inside the
+// band has its high word replaced by a quiet NaN's before it is used: one v_cndmask_b32 per
+// distance. v_min_f64 passes over a NaN and a NaN equals no row minimum, so such a cell offers
+// neither a minimum nor a column, exactly as a +inf would (the walk's minima start from +inf and a
+// row left at +inf is a row without a distance). Groups wholly inside the band are not walked.
+template <int SELF>
+__device__ __forceinline__ double band_mask(double d, bool in_band) {
+  if constexpr (SELF) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, d);
+    const unsigned hi = in_band ? 0x7ff80000u : (unsigned)(u >> 32);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | (unsigned)u);
+  }
+  return d;
+}
+
+template <int PROF, int SELF = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_simple_mfma(
     const double* __restrict__ ext, const double* __restrict__ rec, const int32_t* __restrict__ len,
     const int32_t* __restrict__ pairs, const double* __restrict__ prof, const double* __restrict__ wpad,
     const int64_t* __restrict__ woff, const int64_t* __restrict__ toff, int n2max, int64_t n_pairs, int apply_oti,
     unsigned long long* __restrict__ mpk_g, double* __restrict__ score, int32_t* __restrict__ oti_out,
-    ProfOut<PROF> po) {
+    ProfOut<PROF, SELF> po) {
+  static_assert(!SELF || PROF, "the self-join returns a profile");
   constexpr int L = kFastL;
   extern __shared__ double gsm[];  // 4 waves x 16 x kGS doubles; reused for the final sort
   __shared__ int s_k;
@@ -636,7 +677,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     mpk = mpk_g + (size_t)blockIdx.x * n2max;
     nk = n2max;
   }
-  if (t == 0) {
+  if (!SELF && t == 0) {
     const int best = simple_oti_index(prof + ta * 12, prof + tb * 12);
     s_k = apply_oti ? best : 0;
     if (oti_out) oti_out[p] = best;
@@ -656,7 +697,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   __threadfence();
   __syncthreads();
   if (!live) return;  // whole block (uniform)
-  const int kq = __builtin_amdgcn_readfirstlane(s_k);
+  const int kq = SELF ? 0 : __builtin_amdgcn_readfirstlane(s_k);
   const int64_t oa = toff[ta], ob0 = toff[tb];
   const double* Ea = ext + (size_t)oa * kExt + kq;  // query bin (j + kq) mod 12 at offset j
   const double* Rb = rec + (size_t)ob0 * kRec;
@@ -680,6 +721,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const int li = lane & 15, lk = lane >> 4;  // MFMA operand row / k index
   for (int g = wave; g < NG; g += 4) {
     const int ob = -(P - 1) + g * kDW;  // diagonal of lane 0, k = 0
+    bool band[kKM] = {};               // SELF: diagonal k of this lane is a trivial match
+    if constexpr (SELF) {
+      if (ob >= -po.excl && ob + kDW - 1 <= po.excl) continue;  // the whole group is (wave-uniform)
+#pragma unroll
+      for (int k = 0; k < kKM; ++k) band[k] = abs(ob + kKM * lane + k) <= po.excl;
+    }
     const int x_lo = max(0, -(ob + kDW - 1));
     const int x_hi = min(P - 1, Q - 1 - ob) + L - 1;
     const int yl = ob + kKM * lane;     // column of diagonal k at step x: x + yl + k
@@ -810,7 +857,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
           for (int k = 0; k < kKM; ++k) {
             const double qt = W[k][L - 1] + gall[s][k];
-            m = vmin_f64(m, fma(-2.0, qt, sbv[s + k] + sar));
+            m = vmin_f64(m, band_mask<SELF>(fma(-2.0, qt, sbv[s + k] + sar), band[k]));
           }
         } else {
           const double rmn = __builtin_bit_cast(double,
@@ -820,7 +867,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
           for (int k = kKM - 1; k >= 0; --k) {
             const double qt = W[k][L - 1] + gall[s][k];
-            if (fma(-2.0, qt, sbv[s + k] + sar) == rmn) khit = k;
+            if (band_mask<SELF>(fma(-2.0, qt, sbv[s + k] + sar), band[k]) == rmn) khit = k;
           }
           const unsigned long long hits = __builtin_amdgcn_ballot_w64(khit < kKM);
           // a hit implies a row in [0, P) (rmn is NaN elsewhere) and a column in [0, Q) (sbv is +inf elsewhere)
@@ -865,6 +912,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   __syncthreads();  // every wave's atomics complete (mode 1: the columns are in mpi, and G is free)
   } while (PROF && ++mode < 2);
   // the row-minimum keys into LDS, then the bitonic sort and the median as k_simple_diag
+  if constexpr (SELF) {  // the keys decoded in place; no median
+    for (int i = t; i < nk; i += 256) {
+      const unsigned long long key = __hip_atomic_load(&mpk[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      mpk[i] = __builtin_bit_cast(unsigned long long, dkey_inv(key));
+      if (__hip_atomic_load(&mpi[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == INT32_MAX) mpi[i] = -1;
+    }
+    return;
+  }
   unsigned long long* sk = reinterpret_cast<unsigned long long*>(gsm);
   if constexpr (PROF) {
     // pads sort last; the pair's keys are decoded in place (mp_out) once their copy is taken
@@ -910,6 +965,73 @@ __global__ void k_simple_prof_check(const int32_t* __restrict__ len, const int32
   const int64_t P = max(len[pairs[2 * p]] - L + 1, 0);
   const int64_t lo = prof_off[p], hi = prof_off[p + 1];
   if (lo < 0 || hi < lo || hi > prof_total || P > hi - lo) atomicMin(bad, (unsigned long long)p);
+}
+
+// acoss_simple_self_profile's track list as the pairs (t, t) the profile kernels and the per-track
+// tables take; the first entry outside [0, n_tracks) goes to bad[0] (preset to the largest value)
+// and stands as track 0 in the list, which the caller then refuses before anything reads it.
+__global__ void k_simple_self_pairs(const int32_t* __restrict__ tracks, int64_t n_sel, int n_tracks,
+                                    int32_t* __restrict__ pairs, unsigned long long* __restrict__ bad) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_sel) return;
+  const int t = tracks[p];
+  const bool ok = t >= 0 && t < n_tracks;
+  if (!ok) atomicMin(bad, (unsigned long long)p);
+  pairs[2 * p] = pairs[2 * p + 1] = ok ? t : 0;
+}
+
+// Motif and discord of one self-profile per block: over the rows whose mp is not NaN, the smallest
+// row attaining the minimum of mp with its mpi, and the smallest row attaining the maximum. Ordered
+// by dkey's keys (of mp + 0.0: a -0 orders as +0, as an IEEE compare has it): the block's extreme
+// key first, then the smallest row among the threads that hold it. (-1, -1) and -1 without such a row.
+__global__ __launch_bounds__(256) void k_simple_motif(const int32_t* __restrict__ len, const int32_t* __restrict__ pairs,
+                                                      int L, const int64_t* __restrict__ prof_off,
+                                                      const double* __restrict__ mp, const int32_t* __restrict__ mpi,
+                                                      int32_t* __restrict__ motif, int32_t* __restrict__ discord) {
+  __shared__ unsigned long long s_kmin, s_kmax;
+  __shared__ int s_rmin, s_rmax;
+  const int64_t p = blockIdx.x;
+  const int t = threadIdx.x;
+  const int P = max(len[pairs[2 * p]] - L + 1, 0);
+  const int64_t base = prof_off[p];
+  if (t == 0) {
+    s_kmin = ~0ull;
+    s_kmax = 0ull;
+    s_rmin = INT32_MAX;
+    s_rmax = INT32_MAX;
+  }
+  __syncthreads();
+  unsigned long long kmin = ~0ull, kmax = 0ull;
+  int rmin = INT32_MAX, rmax = INT32_MAX;  // INT32_MAX: this thread saw no row
+  for (int i = t; i < P; i += 256) {
+    const double v = mp[base + i];
+    if (v != v) continue;
+    const unsigned long long key = dkey(v + 0.0);
+    if (rmin == INT32_MAX || key < kmin) {
+      kmin = key;
+      rmin = i;
+    }
+    if (rmax == INT32_MAX || key > kmax) {
+      kmax = key;
+      rmax = i;
+    }
+  }
+  if (rmin != INT32_MAX) {
+    atomicMin(&s_kmin, kmin);
+    atomicMax(&s_kmax, kmax);
+  }
+  __syncthreads();
+  if (rmin != INT32_MAX && kmin == s_kmin) atomicMin(&s_rmin, rmin);
+  if (rmax != INT32_MAX && kmax == s_kmax) atomicMin(&s_rmax, rmax);
+  __syncthreads();
+  if (t == 0) {
+    const bool any = s_rmin != INT32_MAX;
+    if (motif) {
+      motif[2 * p] = any ? s_rmin : -1;
+      motif[2 * p + 1] = any ? mpi[base + s_rmin] : -1;
+    }
+    if (discord) discord[p] = any ? s_rmax : -1;
+  }
 }
 
 int pow2_at_least(int v) {
@@ -1162,6 +1284,95 @@ extern "C" int acoss_simple_profile(const double* feats, const int64_t* track_of
     else
       hipLaunchKernelGGL(k_simple_pair<1>, dim3((unsigned)np), dim3(256), 0, s, feats, track_off, track_len, pp, T.prof,
                          T.wnorm, T.toff, sslen, apply_oti, score_out + p0, oo, po);
+    ACOSS_LAUNCH_CHECK();
+  }
+  prof_end(PH_SIMPLE, s);
+  return ACOSS_OK;
+}
+
+extern "C" int acoss_simple_self_profile(const double* feats, const int64_t* track_off, const int32_t* track_len,
+                                         int32_t n_tracks, int32_t max_len, const int32_t* tracks, int64_t n_sel,
+                                         int32_t sslen, int32_t excl, const int64_t* prof_off, int64_t prof_total,
+                                         double* mp_out, int32_t* mpi_out, int32_t* motif_out, int32_t* discord_out,
+                                         void* hip_stream) {
+  clear_error();
+  if (n_tracks < 0 || n_sel < 0 || prof_total < 0 ||
+      (n_sel > 0 && (!feats || !track_off || !track_len || !tracks || !prof_off)) ||
+      (prof_total > 0 && (!mp_out || !mpi_out))) {
+    set_error("acoss_simple_self_profile: bad arguments");
+    return ACOSS_E_ARG;
+  }
+  if (sslen < 1 || sslen > kMaxL) {
+    set_error("acoss_simple_self_profile: sslen=%d outside [1, %d]", sslen, kMaxL);
+    return ACOSS_E_ARG;
+  }
+  if (excl < 0) {
+    set_error("acoss_simple_self_profile: excl=%d is negative", excl);
+    return ACOSS_E_ARG;
+  }
+  if (max_len > kMaxLen) {
+    set_error("acoss_simple_self_profile: max_len=%d exceeds %d SiMPle frames", max_len, kMaxLen);
+    return ACOSS_E_SHAPE;
+  }
+  if (n_sel == 0) return ACOSS_OK;
+  if (n_tracks == 0) {
+    set_error("acoss_simple_self_profile: track index of entry 0 outside [0, 0)");
+    return ACOSS_E_ARG;
+  }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  prof_begin(PH_SIMPLE, s);
+  // the list as pairs (t, t), its indices checked on the device before anything is indexed by them
+  char* sp = static_cast<char*>(workspace(16, 256 + (size_t)n_sel * 8));
+  if (!sp) return ACOSS_E_HIP;
+  unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(sp);
+  int32_t* pairs = reinterpret_cast<int32_t*>(sp + 256);
+  ACOSS_HIP_CHECK(hipMemsetAsync(d_bad, 0xff, 8, s));
+  hipLaunchKernelGGL(k_simple_self_pairs, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, s, tracks, n_sel,
+                     n_tracks, pairs, d_bad);
+  ACOSS_LAUNCH_CHECK();
+  int64_t bad_sel = -1;
+  ACOSS_HIP_CHECK(hipMemcpyAsync(&bad_sel, d_bad, 8, hipMemcpyDeviceToHost, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  if (bad_sel >= 0) {
+    set_error("acoss_simple_self_profile: track index of entry %lld outside [0, %d)", (long long)bad_sel, n_tracks);
+    return ACOSS_E_ARG;
+  }
+  // kernels as acoss_simple_profile's, in their SELF instantiations
+  const bool fast = sslen == kFastL;
+  SimpleTracks T;
+  int64_t bad = -1;
+  const int trc = simple_tracks(feats, track_off, track_len, n_tracks, pairs, n_sel, sslen, fast, fast, prof_off,
+                                prof_total, &bad, s, &T);
+  if (trc != ACOSS_OK) return trc;
+  if (bad >= 0) {
+    set_error("acoss_simple_self_profile: prof_off of entry %lld is negative, leaves less than the track's profile "
+              "length or ends past prof_total=%lld", (long long)bad, (long long)prof_total);
+    return ACOSS_E_ARG;
+  }
+  const char* benv = getenv("ACOSS_SIMPLE_PROFILE_BATCH");
+  int64_t per = (int64_t)1 << 20;
+  if (benv && atoll(benv) >= 1) per = std::min<int64_t>(atoll(benv), per);
+  const int n2max = pow2_at_least(max(max_len - kFastL + 1, 2));
+  const size_t mlds = (size_t)4 * 16 * kGS * 8;
+  if (fast)
+    ACOSS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_simple_mfma<1, 1>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
+  for (int64_t p0 = 0; p0 < n_sel; p0 += per) {
+    const int64_t np = std::min<int64_t>(n_sel - p0, per);
+    const int32_t* pp = pairs + 2 * p0;
+    const ProfOut<1, 1> po{prof_off + p0, mp_out, mpi_out, excl};
+    if (fast)
+      hipLaunchKernelGGL((k_simple_mfma<1, 1>), dim3((unsigned)np), dim3(256), mlds, s, T.ext, T.rec, track_len, pp,
+                         T.prof, T.wpad, T.woff, T.toff, n2max, np, 0, (unsigned long long*)nullptr, (double*)nullptr,
+                         (int32_t*)nullptr, po);
+    else
+      hipLaunchKernelGGL((k_simple_pair<1, 1>), dim3((unsigned)np), dim3(256), 0, s, feats, track_off, track_len, pp,
+                         T.prof, T.wnorm, T.toff, sslen, 0, (double*)nullptr, (int32_t*)nullptr, po);
+    ACOSS_LAUNCH_CHECK();
+  }
+  if (motif_out || discord_out) {
+    hipLaunchKernelGGL(k_simple_motif, dim3((unsigned)n_sel), dim3(256), 0, s, track_len, pairs, sslen, prof_off, mp_out,
+                       mpi_out, motif_out, discord_out);
     ACOSS_LAUNCH_CHECK();
   }
   prof_end(PH_SIMPLE, s);

@@ -386,6 +386,41 @@ int acoss_simple_profile(const double* feats, const int64_t* track_off, const in
                          const int64_t* prof_off, int64_t prof_total, double* mp_out, int32_t* mpi_out,
                          double* score_out, int32_t* oti_out, void* hip_stream);
 
+/* The SiMPle self-join (Silva et al., ISMIR 2016: the other of the paper's "subsequences joins"):
+ * the matrix profile of a track against itself with the trivial matches excluded, its motif (the
+ * repeated section) and its discord (the most unusual passage). feats, track_off, track_len,
+ * n_tracks and max_len as acoss_simple_profile; tracks: device int32[n_sel], the tracks to profile.
+ * Entry e, track t = tracks[e] of n columns, P = n - sslen + 1: its P rows (none when P <= 0) occupy
+ * mp_out[prof_off[e] .. prof_off[e] + max(P, 0)) and the same range of mpi_out.
+ *
+ * The definition.
+ *   dist(i, j), 0 <= i, j < P, is acoss_simple_profile's canonical distance with query = reference
+ *     = t and no roll (k = 0): a frame dot is the product of bin 0 followed by the fma chain over
+ *     bins 1..11, frame norms likewise, window sums are sequential adds over t = 0..sslen-1,
+ *     dist = (s[j] + s[i]) - 2 qt. (dist(i, j) == dist(j, i) bit for bit, and dist(i, i) == 0.)
+ *   mp[i] = the minimum of dist(i, j) over the j with |i - j| > excl; mpi[i] = the smallest such j
+ *     attaining it (an IEEE compare, the first of equals).
+ *   A row with no admissible distance below +inf holds NaN in mp and -1 in mpi: every row when
+ *     P - 1 <= excl, and rows with NaN features under their window.
+ *   motif_out[2 e .. 2 e + 2) (may be NULL) = (i*, mpi[i*]), i* the smallest row attaining the
+ *     minimum of mp over its rows that are not NaN; discord_out[e] (may be NULL) = the smallest row
+ *     attaining their maximum. Without such a row (-1, -1) and -1.
+ * An entry's output does not depend on its place in the list; a track listed twice fills both of
+ * its ranges identically. No median and no OTI are formed.
+ *
+ * Refusals as acoss_simple_profile (sslen outside 1..16: ACOSS_E_ARG; max_len above 4096:
+ * ACOSS_E_SHAPE; prof_off, device int64[n_sel + 1], checked on the device before any write, the
+ * message naming the first bad entry); in addition excl < 0 or a track index outside
+ * [0, n_tracks) (checked on the device as well, the message naming the first such entry) returns
+ * ACOSS_E_ARG. Nothing is written in any of these cases.
+ * Kernels (simple.hip): the SELF instantiations k_simple_mfma<1, 1> (sslen = 10, every length) and
+ * k_simple_pair<1, 1> (every other sslen) of the profile kernels, then k_simple_motif, one block per
+ * entry. ACOSS_SIMPLE_PROFILE_BATCH applies as in acoss_simple_profile. */
+int acoss_simple_self_profile(const double* feats, const int64_t* track_off, const int32_t* track_len,
+                              int32_t n_tracks, int32_t max_len, const int32_t* tracks, int64_t n_sel, int32_t sslen,
+                              int32_t excl, const int64_t* prof_off, int64_t prof_total, double* mp_out,
+                              int32_t* mpi_out, int32_t* motif_out, int32_t* discord_out, void* hip_stream);
+
 /* Per-track median downsampling of chroma (A13: Serra09/ChenFusion.load_features,
  * acoss/algorithms/rqa_serra09.py:44-53 and latefusion_chen.py:46-56, which call
  * librosa.util.sync(chroma.T, arange(0, n, factor), aggregate=np.median)).
