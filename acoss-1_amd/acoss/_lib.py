@@ -29,6 +29,20 @@ class CrpParams(ctypes.Structure):
                 ("oti", ctypes.c_int32), ("gamma_open", ctypes.c_float), ("gamma_ext", ctypes.c_float)]
 
 
+BINARIZE = {"percentile": 0, "oti": 1}  # ACOSS_BIN_PERCENTILE, ACOSS_BIN_OTI
+
+
+class CrpParams2(ctypes.Structure):
+    """acoss_crp_params2 — acoss_crp_params and the binarisation (include/acoss_hip.h): what the
+    entries ending in 2 take. m, tau, ... read through to the base."""
+    _fields_ = [("base", CrpParams), ("binarize", ctypes.c_int32), ("oti_rank", ctypes.c_int32)]
+
+    def __getattr__(self, name):  # only reached for what the struct itself does not have
+        if name in ("m", "tau", "kappa", "oti", "gamma_open", "gamma_ext"):
+            return getattr(self.base, name)
+        raise AttributeError(name)
+
+
 class NpzMember(ctypes.Structure):
     """acoss_npz_member — one array of an .npz feature file (include/acoss_hip.h)."""
     _fields_ = [("file", ctypes.c_int32), ("method", ctypes.c_int32), ("ndim", ctypes.c_int32),
@@ -100,6 +114,13 @@ SIGNATURES = {
     "acoss_profile_enable": [ctypes.c_int],
     "acoss_profile_read": [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), ctypes.c_int],
 }
+# the entries ending in 2: acoss_crp_params2 in place of acoss_crp_params, every other argument kept
+# (acoss_crp_pair2 gains closer_out before the stream)
+for _name in ("acoss_crp_align", "acoss_crp_locate", "acoss_crp_locate_dmax", "acoss_crp_path", "acoss_crp_path_dmax",
+              "acoss_crp_rqa"):
+    SIGNATURES[_name + "2"] = [ctypes.POINTER(CrpParams2) if a is ctypes.POINTER(CrpParams) else a
+                               for a in SIGNATURES[_name]]
+SIGNATURES["acoss_crp_pair2"] = [_vp, _i32, _vp, _i32, ctypes.POINTER(CrpParams2), _vp, _vp, _vp, _vp, _vp, _vp, _vp]
 
 _lib = None
 
@@ -212,8 +233,37 @@ def _check_knn(J, n):
             raise ValueError("kNN column indices repeat within a row")
 
 
-def crp_params(m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5):
-    return CrpParams(int(m), int(tau), float(kappa), int(bool(oti)), float(gamma_open), float(gamma_ext))
+def check_binarize(binarize, oti_rank):
+    """The (binarize, oti_rank) every layer takes: 'percentile' (essentia's percentile CRP, oti_rank
+    unused) or 'oti' (the OTI-binary CRP of Serra08, oti_rank in 1 .. 12; include/acoss_hip.h,
+    acoss_crp_params2). Returns oti_rank as an int; raises ValueError otherwise."""
+    if binarize not in BINARIZE:
+        raise ValueError("binarize must be one of %s, not %r" % (", ".join(BINARIZE), binarize))
+    if isinstance(oti_rank, bool) or int(oti_rank) != oti_rank or not 1 <= int(oti_rank) <= 12:
+        raise ValueError("oti_rank must be an integer in 1 .. 12, not %r" % (oti_rank,))
+    return int(oti_rank)
+
+
+def binarize_suffix(binarize="percentile", oti_rank=1):
+    """What a cache or result name carries for the binarisation: '' for the percentile CRP, '-otib'
+    for the OTI-binary CRP at rank 1, '-otib<rank>' above."""
+    oti_rank = check_binarize(binarize, oti_rank)
+    if binarize == "percentile":
+        return ""
+    return "-otib" if oti_rank == 1 else "-otib%d" % oti_rank
+
+
+def crp_params(m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, binarize="percentile", oti_rank=1):
+    """acoss_crp_params for the percentile CRP, acoss_crp_params2 for binarize='oti': the crp_* calls
+    below pick the entry point (acoss_crp_align or acoss_crp_align2, ...) by the struct's type."""
+    oti_rank = check_binarize(binarize, oti_rank)
+    base = CrpParams(int(m), int(tau), float(kappa), int(bool(oti)), float(gamma_open), float(gamma_ext))
+    return base if binarize == "percentile" else CrpParams2(base, BINARIZE[binarize], oti_rank)
+
+
+def _entry(name, params):
+    """The library entry `name` for these params: its twin ending in 2 for acoss_crp_params2."""
+    return name + "2" if isinstance(params, CrpParams2) else name
 
 
 # ----------------------------------------------------------------------------------------
@@ -256,14 +306,17 @@ def crp_align(feats, track_off, track_len, max_len, pairs, params, qmax=True, dm
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     want = (("qmax", qmax, "float32"), ("dmax", dmax, "float32"), ("oti", oti, "int32"))
     out = {key: _empty(dtype, P) for key, on, dtype in want if on}
-    rc = load_library().acoss_crp_align(*lead, _ptr(out.get("qmax")), _ptr(out.get("dmax")), _ptr(out.get("oti")),
+    entry = _entry("acoss_crp_align", params)
+    rc = getattr(load_library(), entry)(*lead, _ptr(out.get("qmax")), _ptr(out.get("dmax")), _ptr(out.get("oti")),
                                         _stream())
-    _check(rc, "acoss_crp_align")
+    _check(rc, entry)
     return out
 
 
 def crp_pair(X, Y, params, dist=True):
-    """Single pair with intermediates: dist, thr_row, thr_col, crp (uint8), oti."""
+    """Single pair with intermediates: dist, thr_row, thr_col, crp (uint8), oti. Under binarize='oti'
+    (acoss_crp_pair2) there are no thresholds: dist (D_0), crp, oti and closer (uint8, the count of
+    transpositions strictly closer than the applied one)."""
     torch = _torch()
     lib = load_library()
     X = _dev(X, torch.float32)
@@ -271,6 +324,17 @@ def crp_pair(X, Y, params, dist=True):
     M, N = X.shape[0], Y.shape[0]
     Mp, Np = stacked_len(M, params.m, params.tau), stacked_len(N, params.m, params.tau)
     D = _empty("float32", Mp, Np) if dist else None
+    if isinstance(params, CrpParams2):
+        otib = params.binarize == BINARIZE["oti"]
+        tr, tc = (None, None) if otib else (_empty("float32", Mp), _empty("float32", Np))
+        C, o = _empty("uint8", Mp, Np), _empty("int32", 1)
+        closer = _empty("uint8", Mp, Np) if otib else None
+        rc = lib.acoss_crp_pair2(_ptr(X), M, _ptr(Y), N, ctypes.byref(params), _ptr(D), _ptr(tr), _ptr(tc), _ptr(C),
+                                 _ptr(o), _ptr(closer), _stream())
+        _check(rc, "acoss_crp_pair2")
+        out = {"dist": D, "crp": C, "oti": o}
+        out.update({"closer": closer} if otib else {"thr_row": tr, "thr_col": tc})
+        return out
     tr, tc = _empty("float32", Mp), _empty("float32", Np)
     C, o = _empty("uint8", Mp, Np), _empty("int32", 1)
     rc = lib.acoss_crp_pair(_ptr(X), M, _ptr(Y), N, ctypes.byref(params), _ptr(D), _ptr(tr), _ptr(tc), _ptr(C),
@@ -313,6 +377,7 @@ def crp_locate(feats, track_off, track_len, max_len, pairs, params, align=0):
     (acoss_crp_locate_dmax), the score under "dmax"; its path may begin on an intermediate cell of a
     (2, 1) or (1, 2) step, so i0 or j0 may be 1 (see crp_path)."""
     key, entry = _aligner(align, "acoss_crp_locate")
+    entry = _entry(entry, params)
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     out = {key: _empty("float32", P), "seg": _empty("int32", P, 4), "oti": _empty("int32", P)}
     rc = getattr(load_library(), entry)(*lead, _ptr(out[key]), _ptr(out["seg"]), _ptr(out["oti"]), _stream())
@@ -359,6 +424,7 @@ def crp_path(feats, track_off, track_len, max_len, pairs, params, align=0):
     torch = _torch()
     lib = load_library()
     key, entry = _aligner(align, "acoss_crp_path")
+    entry = _entry(entry, params)
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     pairs = keep[3]
     L = stacked_len(int(max_len), params.m, params.tau)
@@ -417,10 +483,11 @@ def crp_rqa(feats, track_off, track_len, max_len, pairs, params, lmin=2, smax=Tr
         out["smax"] = _empty("float32", P)
     if hist_cap:
         out["hist"] = _empty("int32", P, int(hist_cap))
-    rc = load_library().acoss_crp_rqa(*lead, int(lmin), _ptr(out.get("counts")), _ptr(out.get("lmax")),
-                                      _ptr(out.get("stats")), _ptr(out.get("smax")), _ptr(out["oti"]), int(hist_cap),
-                                      _ptr(out.get("hist")), _stream())
-    _check(rc, "acoss_crp_rqa")
+    entry = _entry("acoss_crp_rqa", params)
+    rc = getattr(load_library(), entry)(*lead, int(lmin), _ptr(out.get("counts")), _ptr(out.get("lmax")),
+                                        _ptr(out.get("stats")), _ptr(out.get("smax")), _ptr(out["oti"]), int(hist_cap),
+                                        _ptr(out.get("hist")), _stream())
+    _check(rc, entry)
     return out
 
 

@@ -11,6 +11,7 @@ import argparse
 
 import numpy as np
 
+from .. import _lib
 from .algorithm_template import CoverAlgorithm
 from .rqa_serra09 import ChromaBackedAlgorithm
 from .utils.similarity_fusion import doSimilarityFusion
@@ -23,10 +24,18 @@ class ChenFusion(ChromaBackedAlgorithm):
     _Ds_on_every_rank = True
     _takes_candidates = False  # the fusion needs every pair's score
 
+    @staticmethod
+    def algorithm_name(binarize="percentile", oti_rank=1):
+        """The name of the Ds cache and the results: 'LateFusionChen' (the reference's), on the
+        OTI-binary CRP 'LateFusionChen-otib', 'LateFusionChen-otib<rank>' above rank 1."""
+        return "LateFusionChen" + _lib.binarize_suffix(binarize, oti_rank)
+
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='benchmark', oti=True, kappa=0.095,
-                 tau=1, m=9, downsample_fac=40, cachedir="cache"):
-        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac)
-        CoverAlgorithm.__init__(self, dataset_csv, name="LateFusionChen", similarity_types=["qmax", "dmax"],
+                 tau=1, m=9, downsample_fac=40, cachedir="cache", binarize="percentile", oti_rank=1):
+        """binarize, oti_rank: as Serra09's (both alignments then run on the OTI-binary CRP)."""
+        name = self.algorithm_name(binarize, oti_rank)
+        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac, binarize, oti_rank)
+        CoverAlgorithm.__init__(self, dataset_csv, name=name, similarity_types=["qmax", "dmax"],
                                 datapath=datapath, shortname=shortname, cachedir=cachedir)
 
     def similarity(self, idxs):

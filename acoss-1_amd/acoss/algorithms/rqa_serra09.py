@@ -24,7 +24,9 @@ __all__ = ["Serra09", "ChromaBackedAlgorithm"]
 class ChromaBackedAlgorithm(CoverAlgorithm):
     """Shared by Serra09 and ChenFusion: cached median-downsampled chroma + a device bank."""
 
-    def _init_chroma(self, chroma_type, oti, kappa, tau, m, downsample_fac):
+    def _init_chroma(self, chroma_type, oti, kappa, tau, m, downsample_fac, binarize="percentile", oti_rank=1):
+        self.oti_rank = _lib.check_binarize(binarize, oti_rank)
+        self.binarize = binarize
         self.oti = oti
         self.tau = tau
         self.m = m
@@ -65,10 +67,14 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
         self.prepare()
         return np.maximum(self._bank.lens.astype(np.int64) - self.m * self.tau, 1)
 
+    def _crp_kw(self):
+        """What every bank call of this algorithm takes: the CRP's parameters and its binarisation."""
+        return dict(m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti, binarize=self.binarize,
+                    oti_rank=self.oti_rank)
+
     def _score_dev(self, idxs, dmax=False):
         self.prepare()
-        return self._bank.crp_align(np.asarray(idxs, np.int32), m=self.m, tau=self.tau, kappa=self.kappa,
-                                    oti=self.oti, qmax=True, dmax=dmax)
+        return self._bank.crp_align(np.asarray(idxs, np.int32), qmax=True, dmax=dmax, **self._crp_kw())
 
     def _score(self, idxs, dmax=False):
         return {k: v.cpu().numpy() for k, v in self._score_dev(idxs, dmax).items()}
@@ -93,7 +99,7 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
         align = self._alignment(alignment)
         self.prepare()
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = self._bank.crp_locate(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti, align=align)
+        r = self._bank.crp_locate(idxs, align=align, **self._crp_kw())
         cells = r["seg"].cpu().numpy()
         qf, rf = segment_frames(cells, self.m, self.tau, self.downsample_fac, self._n_frames[idxs[:, 0]],
                                 self._n_frames[idxs[:, 1]])
@@ -115,7 +121,7 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
         align = self._alignment(alignment)
         self.prepare()
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = self._bank.crp_path(idxs, m=self.m, tau=self.tau, kappa=self.kappa, oti=self.oti, align=align)
+        r = self._bank.crp_path(idxs, align=align, **self._crp_kw())
         pc = r["cells"].cpu().numpy()
         return {alignment: r[alignment].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": r["seg"].cpu().numpy(),
                 "path_off": r["path_off"].cpu().numpy(), "path_cells": pc,
@@ -123,8 +129,8 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
 
     def _rqa_dev(self, idxs, lmin=2, smax=True, hist_cap=0, lines=True):
         self.prepare()
-        return self._bank.crp_rqa(np.asarray(idxs, np.int32).reshape(-1, 2), m=self.m, tau=self.tau, kappa=self.kappa,
-                                  oti=self.oti, lmin=lmin, smax=smax, hist_cap=hist_cap, lines=lines)
+        return self._bank.crp_rqa(np.asarray(idxs, np.int32).reshape(-1, 2), lmin=lmin, smax=smax, hist_cap=hist_cap,
+                                  lines=lines, **self._crp_kw())
 
     def rqa(self, idxs, lmin=2, hist=False):
         """Cross-recurrence quantification of every (query, reference) pair of idxs (the definition:
@@ -156,21 +162,28 @@ class Serra09(ChromaBackedAlgorithm):
     MEASURES = MAXIMA + ("det", "lmean", "entr", "rr")
 
     @classmethod
-    def algorithm_name(cls, measure="qmax"):
+    def algorithm_name(cls, measure="qmax", binarize="percentile", oti_rank=1):
         """The name under which a Serra09 that scores by `measure` keeps its Ds cache and writes its
-        results: 'Serra09' for Qmax (the reference's), 'Serra09-<measure>' for any other."""
+        results: 'Serra09' for Qmax (the reference's), 'Serra09-<measure>' for any other. On the
+        OTI-binary CRP (binarize='oti') 'Serra09-otib', 'Serra09-otib<rank>' above rank 1, comes before
+        the measure: 'Serra09-otib2-det'."""
         if measure not in cls.MEASURES:
             raise ValueError("measure must be one of %s, not %r" % (", ".join(cls.MEASURES), measure))
-        return "Serra09" if measure == "qmax" else "Serra09-%s" % measure
+        name = "Serra09" + _lib.binarize_suffix(binarize, oti_rank)
+        return name if measure == "qmax" else "%s-%s" % (name, measure)
 
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='benchmark', oti=True, kappa=0.095,
-                 tau=1, m=9, downsample_fac=40, cachedir="cache", measure="qmax", lmin=2):
-        name = self.algorithm_name(measure)
+                 tau=1, m=9, downsample_fac=40, cachedir="cache", measure="qmax", lmin=2, binarize="percentile",
+                 oti_rank=1):
+        """binarize='oti': every CRP of this object (similarity, localize, align_path, rqa, measure=,
+        the shortlist flow) is the OTI-binary CRP of Serra08 at oti_rank in 1 .. 12 (include/acoss_hip.h,
+        acoss_crp_params2) in place of the percentile CRP; kappa is then not read."""
+        name = self.algorithm_name(measure, binarize, oti_rank)
         if int(lmin) != lmin or lmin < 1:
             raise ValueError("lmin must be an integer >= 1, not %r" % (lmin,))
         self.measure = measure
         self.lmin = int(lmin)
-        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac)
+        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac, binarize, oti_rank)
         CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name=name, datapath=datapath, shortname=shortname,
                                 cachedir=cachedir)
 

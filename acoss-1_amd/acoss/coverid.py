@@ -21,17 +21,22 @@ _LOG_FILE_PATH = "acoss.coverid.log"
 
 algorithm_names = ["Serra09", "EarlyFusionTraile", "LateFusionChen", "FTM2D", "SiMPle"]
 shortlist_algorithms = ("Serra09", "SiMPle")  # the alignment scorers that take an FTM2D shortlist
+binarize_algorithms = ("Serra09", "LateFusionChen")  # the scorers on a CRP, which take its binarisation
 
 
 def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09", shortname="covers80",
-              parallel=True, n_workers=-1, cachedir="cache", shortlist=None, measure="qmax"):
+              parallel=True, n_workers=-1, cachedir="cache", shortlist=None, measure="qmax", binarize="percentile",
+              oti_rank=1):
     """Run one cover-ID algorithm over a dataset CSV and print/write its evaluation statistics.
     Returns the algorithm object (its Ds hold the similarity matrices).
     shortlist: None, or k: Serra09 / SiMPle score only each song's k best FTM2D candidates (shingles
     made from the same CSV, features, chroma type and cache directory); the entries of Ds they do
     not score are -inf.
     measure: what Serra09 fills Ds with, one of Serra09.MEASURES ('qmax', the reference's, 'smax', 'lmax',
-    'det', 'lmean', 'entr', 'rr'); any other than 'qmax' runs, caches and reports as 'Serra09-<measure>'."""
+    'det', 'lmean', 'entr', 'rr'); any other than 'qmax' runs, caches and reports as 'Serra09-<measure>'.
+    binarize, oti_rank: Serra09 / LateFusionChen on the OTI-binary CRP of Serra08 (binarize='oti', oti_rank in
+    1 .. 12; include/acoss_hip.h, acoss_crp_params2) in place of the percentile CRP; they run, cache and report
+    as 'Serra09-otib', 'LateFusionChen-otib', with the rank appended above 1."""
     logger = log(_LOG_FILE_PATH)
     if algorithm not in algorithm_names and algorithm != "EarlyFusion":
         warn = ("acoss.coverid: Couldn't find '%s' algorithm in acoss Available cover id algorithms are %s "
@@ -43,6 +48,11 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
                          % (" and ".join(shortlist_algorithms), algorithm))
     if measure != "qmax" and algorithm != "Serra09":
         raise ValueError("measure is supported by Serra09 only, not by '%s'" % algorithm)
+    from ._lib import check_binarize
+    oti_rank = check_binarize(binarize, oti_rank)
+    if (binarize != "percentile" or oti_rank != 1) and algorithm not in binarize_algorithms:
+        raise ValueError("binarize and oti_rank are supported by %s only, not by '%s'"
+                         % (" and ".join(binarize_algorithms), algorithm))
     logger.info("Running acoss cover identification benchmarking for the algorithm - '%s'" % algorithm)
     start = time.monotonic()
     kw = dict(dataset_csv=dataset_csv, datapath=feature_dir, chroma_type=feature_type, shortname=shortname,
@@ -59,7 +69,7 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         del first
     if algorithm == "Serra09":
         from .algorithms.rqa_serra09 import Serra09
-        algo = Serra09(measure=measure, **kw)
+        algo = Serra09(measure=measure, binarize=binarize, oti_rank=oti_rank, **kw)
         logger.info('Computing pairwise similarity...')
         algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True, candidates=candidates)
         algo.normalize_by_length()
@@ -75,7 +85,7 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         algo.do_late_fusion()
     elif algorithm == "LateFusionChen":
         from .algorithms.latefusion_chen import ChenFusion
-        algo = ChenFusion(**kw)
+        algo = ChenFusion(binarize=binarize, oti_rank=oti_rank, **kw)
         logger.info('Computing pairwise similarity...')
         algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True)
         algo.normalize_by_length()
@@ -120,6 +130,11 @@ def parser_args(cmd_args):
     parser.add_argument("-n", '--n_workers', type=int, action="store", default=-1, help="Accepted for compatibility")
     parser.add_argument("-k", '--shortlist', type=int, action="store", default=None,
                         help="Serra09 / SiMPle: score only each song's K best FTM2D candidates")
+    parser.add_argument('--binarize', type=str, choices=("percentile", "oti"), action="store", default="percentile",
+                        help="Serra09 / LateFusionChen: the percentile CRP or the OTI-binary CRP (Serra08)")
+    parser.add_argument('--oti-rank', type=int, action="store", default=1,
+                        help="with --binarize oti: a cell is a hit when fewer than this many further "
+                             "transpositions are closer (1 .. 12)")
     return parser.parse_args(cmd_args)
 
 
@@ -127,4 +142,4 @@ if __name__ == '__main__':
     args = parser_args(sys.argv[1:])
     benchmark(dataset_csv=args.dataset_csv, feature_dir=args.feature_dir, feature_type=args.chroma_type,
               algorithm=args.method, shortname=args.shortname, parallel=bool(args.parallel), n_workers=args.n_workers,
-              shortlist=args.shortlist)
+              shortlist=args.shortlist, binarize=args.binarize, oti_rank=args.oti_rank)

@@ -121,12 +121,13 @@ class ChromaBank:
 
     def _crp(self, fn, empty, pairs, crp, **want):
         """The three scorers below: fn = the _lib function (want: its output switches); empty = (key,
-        shape, dtype name) of what it returns, for an empty pair list; crp = crp_params' arguments."""
+        shape, dtype name) of what it returns, for an empty pair list; crp = crp_params' arguments, the
+        last two of them (binarize, oti_rank)."""
         torch = _lib._torch()
+        params = _lib.crp_params(*crp)  # also the check of binarize and oti_rank
         pairs = self._pairs(pairs, crp[0], crp[1])
         if pairs is None:
             return {k: torch.zeros(shape, dtype=getattr(torch, dt), device="cuda") for k, shape, dt in empty}
-        params = _lib.crp_params(*crp)
         return fn(self.feats, self.off, self.len, self.max_len, pairs, params, **want)
 
     @staticmethod
@@ -135,29 +136,35 @@ class ChromaBank:
         return ((_lib.score_key(align), 0, "float32"), ("seg", (0, 4), "int32"), ("oti", 0, "int32"))
 
     def crp_align(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, qmax=True,
-                  dmax=False, want_oti=False):
-        """Serra09 (Qmax) / Chen (dmax) scores for (query, reference) pairs."""
+                  dmax=False, want_oti=False, binarize="percentile", oti_rank=1):
+        """Serra09 (Qmax) / Chen (dmax) scores for (query, reference) pairs. binarize='oti': on the
+        OTI-binary CRP of Serra08 at oti_rank (include/acoss_hip.h, acoss_crp_params2; kappa is then
+        not read) in place of the percentile CRP; the same two arguments on the three methods below."""
         empty = [(k, 0, dt) for k, dt, on in (("qmax", "float32", qmax), ("dmax", "float32", dmax),
                                               ("oti", "int32", want_oti)) if on]
-        return self._crp(_lib.crp_align, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext),
+        return self._crp(_lib.crp_align, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank),
                          qmax=qmax, dmax=dmax, oti=want_oti)
 
-    def crp_locate(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0):
+    def crp_locate(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0,
+                   binarize="percentile", oti_rank=1):
         """Qmax of (query, reference) pairs and where it lies: {"qmax", "seg" (P, 4), "oti"} device
         tensors (see _lib.crp_locate); the scores are crp_align's. align=1: dmax and the chen17
         alignment, the score under "dmax"."""
-        return self._crp(_lib.crp_locate, self._located(align), pairs, (m, tau, kappa, oti, gamma_open, gamma_ext),
-                         align=align)
+        return self._crp(_lib.crp_locate, self._located(align), pairs,
+                         (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank), align=align)
 
-    def crp_path(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0):
+    def crp_path(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0,
+                 binarize="percentile", oti_rank=1):
         """Qmax of (query, reference) pairs with the whole alignment path of each: {"qmax", "seg"
         (P, 4), "oti", "path_off" (P + 1,), "cells" (total, 2)} device tensors (see _lib.crp_path);
         scores and segments are crp_locate's. align=1: dmax and the chen17 path, the score under
         "dmax"; its steps also include (1, 0) and (0, 1) and i0 or j0 may be 1 (_lib.crp_path)."""
         empty = self._located(align) + (("path_off", 1, "int64"), ("cells", (0, 2), "int32"))
-        return self._crp(_lib.crp_path, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext), align=align)
+        return self._crp(_lib.crp_path, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank),
+                         align=align)
 
-    def crp_rqa(self, pairs, m=9, tau=1, kappa=0.095, oti=True, lmin=2, smax=True, hist_cap=0, lines=True):
+    def crp_rqa(self, pairs, m=9, tau=1, kappa=0.095, oti=True, lmin=2, smax=True, hist_cap=0, lines=True,
+                binarize="percentile", oti_rank=1):
         """Cross-recurrence quantification of (query, reference) pairs: {"counts" (P, 4), "lmax",
         "stats" (P, 4), "oti"} device tensors, with smax "smax", with hist_cap > 0 "hist"
         (P, hist_cap) (see _lib.crp_rqa); the CRP is crp_align's. lines=False: "oti" and "smax" only."""
@@ -168,5 +175,5 @@ class ChromaBank:
             empty.append(("smax", 0, "float32"))
         if hist_cap:
             empty.append(("hist", (0, int(hist_cap)), "int32"))
-        return self._crp(_lib.crp_rqa, empty, pairs, (m, tau, kappa, oti, 0.5, 0.5), lmin=lmin, smax=smax,
-                         hist_cap=hist_cap, lines=lines)
+        return self._crp(_lib.crp_rqa, empty, pairs, (m, tau, kappa, oti, 0.5, 0.5, binarize, oti_rank), lmin=lmin,
+                         smax=smax, hist_cap=hist_cap, lines=lines)

@@ -22,6 +22,8 @@
 //    later evaluated in the squared domain (sq_threshold), so no per-cell sqrt is needed.
 //  * k_crp_panel: recomputes the distances of a 32-row x 256-column panel and writes the
 //    CRP as one 32-bit word per (32-row strip, column): the layout the DP consumes.
+// Under ACOSS_BIN_OTI (the entries ending in 2) crp_masks runs a third producer of the same words,
+// crp_otib.hip's k_crp_otib, in place of both: no thresholds, no rolled reference, no key planes.
 // The wavefront DP over those words (k_crp_dp*, k_crp_dp_trace for acoss_crp_locate /
 // acoss_locate_crp, k_crp_dp_dir and k_crp_backtrack for acoss_crp_path / acoss_path_crp, each also
 // for chen17 under the _dmax entries) is crp_dp.hip; this file reaches it through launch_dp,
@@ -500,13 +502,33 @@ enum CrpSlot {
   SLOT_RQA = 29, SLOT_RQA_CRP = 30,
 };
 
-int check_params(const acoss_crp_params* P) {
-  if (!P) {
+// Every driver below takes the wide params; the entries without a 2 widen theirs (binarize = 0).
+// Returns NULL for NULL, which check_params then refuses.
+const acoss_crp_params2* widen(const acoss_crp_params* P, acoss_crp_params2& W) {
+  if (!P) return nullptr;
+  W = acoss_crp_params2{*P, ACOSS_BIN_PERCENTILE, 1};
+  return &W;
+}
+
+bool otib(const acoss_crp_params2* P2) { return P2->binarize == ACOSS_BIN_OTI; }
+
+int check_params(const acoss_crp_params2* P2) {
+  if (!P2) {
     set_error("params is NULL");
     return ACOSS_E_ARG;
   }
-  if (P->m < 1 || P->m > 64 || P->tau < 1 || !(P->kappa >= 0.0f && P->kappa <= 1.0f)) {
+  const acoss_crp_params* P = &P2->base;
+  if (P2->binarize != ACOSS_BIN_PERCENTILE && P2->binarize != ACOSS_BIN_OTI) {
+    set_error("unknown binarize %d (ACOSS_BIN_PERCENTILE = 0, ACOSS_BIN_OTI = 1)", P2->binarize);
+    return ACOSS_E_ARG;
+  }
+  // kappa is not read under ACOSS_BIN_OTI
+  if (P->m < 1 || P->m > 64 || P->tau < 1 || (!otib(P2) && !(P->kappa >= 0.0f && P->kappa <= 1.0f))) {
     set_error("unsupported params m=%d tau=%d kappa=%g", P->m, P->tau, (double)P->kappa);
+    return ACOSS_E_ARG;
+  }
+  if (otib(P2) && (P2->oti_rank < 1 || P2->oti_rank > 12)) {
+    set_error("oti_rank %d outside 1 .. 12", P2->oti_rank);
     return ACOSS_E_ARG;
   }
   return ACOSS_OK;
@@ -592,7 +614,9 @@ struct CrpPlan {
   hipStream_t ss[3];
 };
 
-int crp_plan(int m, int tau, int max_len, int64_t n_pairs, hipStream_t s, CrpPlan& P) {
+// otib: the plan of an OTI-binary call (crp_otib.hip makes the masks): no select stripe to fit, no
+// split path and so no key planes.
+int crp_plan(int m, int tau, int max_len, int64_t n_pairs, bool otib, hipStream_t s, CrpPlan& P) {
   const int L = stacked_len(max_len, m, tau);
   if (L <= 0) {
     set_error("max_len %d too short for m=%d tau=%d", max_len, m, tau);
@@ -602,7 +626,7 @@ int crp_plan(int m, int tau, int max_len, int64_t n_pairs, hipStream_t s, CrpPla
   P.tau = tau;
   P.L = L;
   const int ld = P.ld = (int)align_up((size_t)L, 8);  // x16 B = 128 B: band rows never share a cache line
-  P.R = pick_R(m, ld);
+  P.R = otib ? 1 : pick_R(m, ld);
   if (P.R <= 0) {
     set_error("track too long for the LDS stripe (stacked length %d)", ld);
     return ACOSS_E_SHAPE;
@@ -610,8 +634,10 @@ int crp_plan(int m, int tau, int max_len, int64_t n_pairs, hipStream_t s, CrpPla
   P.sel_lds = select_lds_bytes(P.R, m, ld);
   P.pan_lds = panel_lds_floats(32, m) * sizeof(float);
   int rc;
-  if ((rc = set_lds(k_crp_select<false>, P.sel_lds))) return rc;
-  if ((rc = set_lds(k_crp_select<true>, P.sel_lds))) return rc;
+  if (!otib) {
+    if ((rc = set_lds(k_crp_select<false>, P.sel_lds))) return rc;
+    if ((rc = set_lds(k_crp_select<true>, P.sel_lds))) return rc;
+  }
   if ((rc = set_lds(k_crp_panel<0>, P.pan_lds))) return rc;
   if ((rc = set_lds(k_crp_panel<1>, P.pan_lds))) return rc;
   P.nstrips = (L + 31) / 32;
@@ -622,7 +648,7 @@ int crp_plan(int m, int tau, int max_len, int64_t n_pairs, hipStream_t s, CrpPla
   // split path (one sweep + two line-select kernels, crp_split.hip) needs 16-bit key planes;
   // ACOSS_CRP_PATH=generic keeps a shape it covers on the generic kernels
   static const char* path_env = getenv("ACOSS_CRP_PATH");
-  P.split = m == 9 && tau == 1 && L <= 4096 && !(path_env && strcmp(path_env, "generic") == 0);
+  P.split = !otib && m == 9 && tau == 1 && L <= 4096 && !(path_env && strcmp(path_env, "generic") == 0);
   // row pitch: the selects' 32-element runs end at align32(L); one pad column beyond them takes
   // the sweep's branchless out-of-range stores
   P.ldk = (int)align_up(align_up((size_t)L, 32) + 1, 64);
@@ -695,14 +721,24 @@ CrpBatch batch_view(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int
 
 // One DP batch (nb <= C.nb_alloc pairs at pb) up to its CRP: OTI, rolled references, row and
 // column thresholds (thr_*, T_*) and the mask words, on stream s. The one place that chooses
-// between the split path and the generic kernels.
-int crp_masks(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int nb, const acoss_crp_params* params,
+// between the split path, the generic kernels and, under ACOSS_BIN_OTI, the OTI-binary kernel, which
+// needs neither the rolled references nor thresholds (thr_*, T_* are then not written).
+int crp_masks(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int nb, const acoss_crp_params2* params2,
               hipStream_t s) {
   int rc;
+  const acoss_crp_params* params = &params2->base;
   prof_begin(PH_OTI, s);
   hipLaunchKernelGGL(k_pair_oti, dim3((nb + 255) / 256), dim3(256), 0, s, T.prof, T.len, pb, (int64_t)nb, params->oti,
                      C.m, C.tau, C.oti, C.dims);
   ACOSS_LAUNCH_CHECK();
+  if (otib(params2)) {
+    prof_end(PH_OTI, s);
+    prof_begin(PH_MASK, s);
+    if ((rc = launch_otib(batch_view(C, T, pb, 0), nb, C.L, params2->oti_rank, C.mask, C.mask_stride, C.ld, s)))
+      return rc;
+    prof_end(PH_MASK, s);
+    return ACOSS_OK;
+  }
   hipLaunchKernelGGL(k_rotate_ref, dim3(16, nb), dim3(256), 0, s, T.feats, T.off, T.len, pb, C.oti, C.yrot,
                      C.yrot_stride);
   ACOSS_LAUNCH_CHECK();
@@ -775,10 +811,11 @@ const auto no_hook = [](auto&&...) { return ACOSS_OK; };
 //   dp(C, base, nb)  launches the entry's DP for pairs [base, base + nb) under its own phases.
 template <class Check, class Setup, class Dp>
 int crp_batches(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
-                int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2,
                 hipStream_t s, int32_t* oti_out, Check check, Setup setup, Dp dp) {
-  int rc = check_params(params);
+  int rc = check_params(params2);
   if (rc) return rc;
+  const acoss_crp_params* params = &params2->base;
   if (n_pairs < 0 || n_tracks < 0 || max_len < 0) {
     set_error("negative size");
     return ACOSS_E_ARG;
@@ -790,7 +827,7 @@ int crp_batches(const float* feats, const int64_t* track_off, const int32_t* tra
   }
   if ((rc = check())) return rc;
   CrpPlan C;
-  if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, s, C))) return rc;
+  if ((rc = crp_plan(params->m, params->tau, max_len, n_pairs, otib(params2), s, C))) return rc;
   TrackPrep T;
   prof_begin(PH_PREP, s);
   if ((rc = run_prep(feats, track_off, track_len, n_tracks, max_len, C.m, C.tau, s, &T))) return rc;
@@ -799,7 +836,7 @@ int crp_batches(const float* feats, const int64_t* track_off, const int32_t* tra
   if ((rc = setup(C, nbd))) return rc;
   for (int64_t base = 0; base < n_pairs; base += nbd) {
     const int nb = (int)((n_pairs - base) < nbd ? (n_pairs - base) : nbd);
-    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params, s))) return rc;
+    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params2, s))) return rc;
     if ((rc = dp(C, base, nb))) return rc;
     if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
   }
@@ -897,16 +934,21 @@ int empty_matrix_answer(float* score_out, int32_t* seg_out, int32_t* len_out, in
 
 using namespace acoss;
 
-extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, const int32_t* track_len,
-                               int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
-                               const acoss_crp_params* params, float* qmax_out, float* dmax_out, int32_t* oti_out,
-                               void* hip_stream) {
+// The bodies of the entries that make a CRP from chroma take the wide params (params2; params is
+// its base, NULL with it and then refused before anything reads it); each serves the entry without
+// a 2, which widens its params, and its twin.
+namespace {
+
+int crp_align_any(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                  int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2,
+                  float* qmax_out, float* dmax_out, int32_t* oti_out, void* hip_stream) {
   clear_error();
+  const acoss_crp_params* params = params2 ? &params2->base : nullptr;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   float* const out[2] = {qmax_out, dmax_out};  // by launch_dp's align: 0 = Qmax, 1 = dmax
   const int phase[2] = {PH_DP_QMAX, PH_DP_DMAX};
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out, no_hook, no_hook,
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out, no_hook, no_hook,
       [&](const CrpPlan& C, int64_t base, int nb) {
         for (int align = 0; align < 2; ++align) {
           if (!out[align]) continue;
@@ -920,12 +962,20 @@ extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, con
       });
 }
 
-extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params* params,
-                              float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti,
-                              void* hip_stream) {
+int crp_pair_any(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params2* params2, float* dist,
+                 float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti, uint8_t* closer_out, void* hip_stream) {
   clear_error();
-  int rc = check_params(params);
+  int rc = check_params(params2);
   if (rc) return rc;
+  const acoss_crp_params* params = &params2->base;
+  if (otib(params2) && (thr_row || thr_col)) {
+    set_error("thr_row and thr_col must be NULL under ACOSS_BIN_OTI: it has no thresholds");
+    return ACOSS_E_ARG;
+  }
+  if (!otib(params2) && closer_out) {
+    set_error("closer_out must be NULL under ACOSS_BIN_PERCENTILE");
+    return ACOSS_E_ARG;
+  }
   const int m = params->m, tau = params->tau;
   const int Mp = stacked_len(M, m, tau), Np = stacked_len(N, m, tau);
   if (Mp <= 0 || Np <= 0) {
@@ -935,7 +985,7 @@ extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const int max_len = M > N ? M : N;
   CrpPlan C;
-  if ((rc = crp_plan(m, tau, max_len, 1, s, C))) return rc;
+  if ((rc = crp_plan(m, tau, max_len, 1, otib(params2), s, C))) return rc;
   const size_t fbytes = align_up((size_t)(M + N) * 12 * 4, 256);
   char* ws = static_cast<char*>(workspace(SLOT_PAIR, fbytes + 256));
   if (!ws) return ACOSS_E_HIP;
@@ -955,8 +1005,8 @@ extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t
   ACOSS_HIP_CHECK(hipMemcpy(d_pairs, h_pairs, sizeof(h_pairs), hipMemcpyHostToDevice));
   TrackPrep T;
   if ((rc = run_prep(f, d_off, d_len, 2, max_len, m, tau, s, &T))) return rc;
-  if ((rc = crp_masks(C, T, d_pairs, 1, params, s))) return rc;
-  if (dist) {
+  if ((rc = crp_masks(C, T, d_pairs, 1, params2, s))) return rc;
+  if (dist) {  // the roll is the pair's OTI, read from the track itself: under ACOSS_BIN_OTI this is D_0
     hipLaunchKernelGGL(k_crp_panel<1>, dim3((Np + kPanelW - 1) / kPanelW, C.nstrips, 1), dim3(256), C.pan_lds, s,
                        batch_view(C, T, d_pairs, 0), C.T_r, C.T_c, C.thr_stride, C.mask, C.mask_stride, C.ld, dist);
     ACOSS_LAUNCH_CHECK();
@@ -965,11 +1015,47 @@ extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t
     hipLaunchKernelGGL(k_unpack_mask, dim3((Np + 255) / 256, Mp), dim3(256), 0, s, C.mask, C.ld, Mp, Np, crp);
     ACOSS_LAUNCH_CHECK();
   }
+  // after crp was unpacked from the batch kernel's words: the counting kernel writes them once more
+  if (closer_out && (rc = launch_otib(batch_view(C, T, d_pairs, 0), 1, C.L, params2->oti_rank, C.mask, C.mask_stride,
+                                      C.ld, s, closer_out)))
+    return rc;
   if (thr_row) ACOSS_HIP_CHECK(hipMemcpyAsync(thr_row, C.thr_r, 4 * (size_t)Mp, hipMemcpyDeviceToDevice, s));
   if (thr_col) ACOSS_HIP_CHECK(hipMemcpyAsync(thr_col, C.thr_c, 4 * (size_t)Np, hipMemcpyDeviceToDevice, s));
   if (oti) ACOSS_HIP_CHECK(hipMemcpyAsync(oti, C.oti, 4, hipMemcpyDeviceToDevice, s));
   ACOSS_HIP_CHECK(hipStreamSynchronize(s));
   return ACOSS_OK;
+}
+
+}  // namespace
+
+extern "C" int acoss_crp_align(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                               int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                               const acoss_crp_params* params, float* qmax_out, float* dmax_out, int32_t* oti_out,
+                               void* hip_stream) {
+  acoss_crp_params2 W;
+  return crp_align_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), qmax_out,
+                       dmax_out, oti_out, hip_stream);
+}
+
+extern "C" int acoss_crp_align2(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                const acoss_crp_params2* params, float* qmax_out, float* dmax_out, int32_t* oti_out,
+                                void* hip_stream) {
+  return crp_align_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, qmax_out, dmax_out,
+                       oti_out, hip_stream);
+}
+
+extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params* params,
+                              float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti,
+                              void* hip_stream) {
+  acoss_crp_params2 W;
+  return crp_pair_any(X, M, Y, N, widen(params, W), dist, thr_row, thr_col, crp, oti, nullptr, hip_stream);
+}
+
+extern "C" int acoss_crp_pair2(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params2* params,
+                               float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti,
+                               uint8_t* closer_out, void* hip_stream) {
+  return crp_pair_any(X, M, Y, N, params, dist, thr_row, thr_col, crp, oti, closer_out, hip_stream);
 }
 
 extern "C" int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t align, float gamma_open,
@@ -1014,19 +1100,18 @@ int check_rqa_line(int longest) {
   return ACOSS_E_SHAPE;
 }
 
-}  // namespace
-
-extern "C" int acoss_crp_rqa(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
-                             int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
-                             int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
-                             int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
+int crp_rqa_any(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2, int32_t lmin,
+                int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out, int32_t* oti_out,
+                int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
   clear_error();
+  const acoss_crp_params* params = params2 ? &params2->base : nullptr;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const bool lines = counts_out || lmax_out || stats_out || hist_out;
   void* rb = nullptr;  // band-boundary records of the line walk, rstride per pair
   int64_t rstride = 0;
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out,
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out,
       [&] {
         if (int rc = check_rqa_args("acoss_crp_rqa", lmin, hist_cap, hist_out)) return rc;
         return lines ? check_rqa_line(stacked_len(max_len, params->m, params->tau)) : ACOSS_OK;
@@ -1055,6 +1140,25 @@ extern "C" int acoss_crp_rqa(const float* feats, const int64_t* track_off, const
         }
         return ACOSS_OK;
       });
+}
+
+}  // namespace
+
+extern "C" int acoss_crp_rqa(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                             int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                             int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                             int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
+  acoss_crp_params2 W;
+  return crp_rqa_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), lmin, counts_out,
+                     lmax_out, stats_out, smax_out, oti_out, hist_cap, hist_out, hip_stream);
+}
+
+extern "C" int acoss_crp_rqa2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                              int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
+                              int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                              int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
+  return crp_rqa_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, lmin, counts_out,
+                     lmax_out, stats_out, smax_out, oti_out, hist_cap, hist_out, hip_stream);
 }
 
 extern "C" int acoss_rqa_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t lmin, int64_t* counts_out,
@@ -1112,14 +1216,15 @@ int path_bound(int align, int M, int N) { return align == 0 ? (M < N ? M : N) : 
 
 int crp_locate_any(int align, const float* feats, const int64_t* track_off, const int32_t* track_len,
                    int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
-                   const acoss_crp_params* params, float* score_out, int32_t* seg_out, int32_t* oti_out,
+                   const acoss_crp_params2* params2, float* score_out, int32_t* seg_out, int32_t* oti_out,
                    void* hip_stream) {
   clear_error();
+  const acoss_crp_params* params = params2 ? &params2->base : nullptr;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   void* tb = nullptr;  // band-boundary records of the tracing DP, tstride per pair
   int64_t tstride = 0;
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out,
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out,
       [&] {
         if (!seg_out) {
           set_error("seg_out is NULL");
@@ -1162,10 +1267,11 @@ int locate_crp_any(int align, const char* entry, const uint8_t* crp, int32_t M, 
 }
 
 int crp_path_any(int align, const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
-                 int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params* params,
+                 int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2,
                  float* score_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
                  int32_t* path_out, void* hip_stream) {
   clear_error();
+  const acoss_crp_params* params = params2 ? &params2->base : nullptr;
   if (path_cap < 0) {
     set_error("negative size");
     return ACOSS_E_ARG;
@@ -1176,7 +1282,7 @@ int crp_path_any(int align, const float* feats, const int64_t* track_off, const 
   uint32_t* endkey = nullptr;
   int64_t pstride = 0, bstride = 0;
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, s, oti_out,
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out,
       [&] {
         if (!len_out || !path_out) {
           set_error("len_out or path_out is NULL");
@@ -1267,6 +1373,15 @@ extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, co
                                 int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
                                 const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                                 void* hip_stream) {
+  acoss_crp_params2 W;
+  return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), qmax_out,
+                        seg_out, oti_out, hip_stream);
+}
+
+extern "C" int acoss_crp_locate2(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                 int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                 const acoss_crp_params2* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                                 void* hip_stream) {
   return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, qmax_out, seg_out,
                         oti_out, hip_stream);
 }
@@ -1275,6 +1390,15 @@ extern "C" int acoss_crp_locate_dmax(const float* feats, const int64_t* track_of
                                      int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
                                      const acoss_crp_params* params, float* dmax_out, int32_t* seg_out,
                                      int32_t* oti_out, void* hip_stream) {
+  acoss_crp_params2 W;
+  return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), dmax_out,
+                        seg_out, oti_out, hip_stream);
+}
+
+extern "C" int acoss_crp_locate_dmax2(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                      int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                      const acoss_crp_params2* params, float* dmax_out, int32_t* seg_out,
+                                      int32_t* oti_out, void* hip_stream) {
   return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, dmax_out, seg_out,
                         oti_out, hip_stream);
 }
@@ -1293,6 +1417,15 @@ extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, cons
                               int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
                               const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                               int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  acoss_crp_params2 W;
+  return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), qmax_out,
+                      seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
+}
+
+extern "C" int acoss_crp_path2(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                               int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                               const acoss_crp_params2* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                               int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
   return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, qmax_out, seg_out,
                       oti_out, path_cap, len_out, path_out, hip_stream);
 }
@@ -1301,6 +1434,16 @@ extern "C" int acoss_crp_path_dmax(const float* feats, const int64_t* track_off,
                                    int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
                                    const acoss_crp_params* params, float* dmax_out, int32_t* seg_out, int32_t* oti_out,
                                    int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  acoss_crp_params2 W;
+  return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), dmax_out,
+                      seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
+}
+
+extern "C" int acoss_crp_path_dmax2(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                    int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                    const acoss_crp_params2* params, float* dmax_out, int32_t* seg_out,
+                                    int32_t* oti_out, int32_t path_cap, int32_t* len_out, int32_t* path_out,
+                                    void* hip_stream) {
   return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, dmax_out, seg_out,
                       oti_out, path_cap, len_out, path_out, hip_stream);
 }

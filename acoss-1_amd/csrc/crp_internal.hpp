@@ -35,6 +35,14 @@ int launch_crp_split(const CrpBatch& B, int nb, int L, float kappa, void* kplane
                      uint32_t* RT, float* thr_r, float* T_r, float* thr_c, float* T_c, int64_t thr_stride,
                      uint32_t* maskT, int64_t mask_stride, int ld, hipStream_t s);
 
+// The OTI-binary CRP (crp_otib.hip k_crp_otib; the definition: include/acoss_hip.h, acoss_crp_params2):
+// the mask words of nb pairs with stacked lengths of at most L, in the layout the DP consumes, the
+// zero bits above M' in a pair's last strip included. B.oti holds the pairs' global OTI; B.yrot and
+// B.feats2 are not read. Every m <= 64 and every tau. closer (one pair only, may be NULL): the
+// (M' x N') uint8 counts of the transpositions strictly closer than the applied one.
+int launch_otib(const CrpBatch& B, int nb, int L, int oti_rank, uint32_t* maskT, int64_t mask_stride, int ld,
+                hipStream_t s, uint8_t* closer = nullptr);
+
 // The alignment DP (crp_dp.hip) over nb pairs' CRP words maskT (mstride words between pairs, row
 // pitch ld, dims = (M', N') per pair, L = the longest M').
 // launch_dp: align 0 = Qmax (serra09), 1 = dmax (chen17); eqg: go == ge; bnd: ceil(L / 2048) * ld

@@ -42,6 +42,53 @@ typedef struct acoss_crp_params {
   float gamma_ext;    /* disExtension, default 0.5 */
 } acoss_crp_params;
 
+/* How the two chroma sequences become a binary matrix. acoss_crp_params keeps its layout; the
+ * entries ending in 2 (below, after acoss_crp_rqa) take this wider struct and every other argument
+ * of the entry they are the twin of.
+ *   ACOSS_BIN_PERCENTILE: essentia ChromaCrossSimilarity(binarizePercentile=kappa, oti), the mutual
+ *     row / column percentile CRP of the entries without a 2. oti_rank is ignored.
+ *   ACOSS_BIN_OTI: the chroma binary similarity of Serra, Gomez, Herrera and Serra, "Chroma binary
+ *     similarity and local alignment applied to cover song identification" (IEEE TASLP 2008), the
+ *     mode essentia reaches with otiBinary=True. kappa is not read.
+ *
+ * The definition of ACOSS_BIN_OTI, for a pair (query X, reference Y), m, tau, oti and
+ * oti_rank in 1 .. 12:
+ *   g = the pair's global OTI exactly as under the percentile CRP (what oti_out reports); 0 when
+ *     oti = 0.
+ *   D_k(i, j), k = 0 .. 11: the canonical stacked distance of stacked query frame i and stacked
+ *     reference frame j with every reference frame rolled by (g + k) mod 12: the float32 value
+ *     acoss_crp_pair writes to dist for that roll, bit for bit. That is the fmaf chain over the 12
+ *     chroma bins in bin order, the m window taps added in tap order, then
+ *     (N_query - 2 dot) + N_reference clamped at +0, N the per-track stacked squared norms of the
+ *     UN-rolled track, then the correctly rounded square root. It equals
+ *     oracle.crp_dist(X, Y, (g + k) % 12, m, tau).
+ *   closer(i, j) = #{k in 1 .. 11 : D_k(i, j) < D_0(i, j)}, a strict comparison of those float32
+ *     values.
+ *   C(i, j) = 1 iff closer(i, j) < oti_rank.
+ * Consequences:
+ *   oti_rank = 1 is "transposition 0 is the best, the first maximum wins", Serra08's rule: among
+ *     equal distances the smallest shift wins, as np.argmax does in get_oti.
+ *   oti_rank = 12 gives all ones; the masks are nested in oti_rank.
+ *   A stacked frame that is all zero, on either side, makes all twelve distances equal: its whole
+ *     row or column is 1.
+ *   Distinct squared distances may round to the same square root; they then count as equal.
+ *   The dims M', N' are those of the percentile CRP: ceil((n - m tau) / tau).
+ * The definition is on distances, not on dot products: the distance is what the oracle exposes and
+ * the kernels reproduce bit for bit. It is this project's own. Parity with essentia's otiBinary is
+ * NOT pinned (as for the percentile CRP): whether essentia stacks the frames before the per-cell
+ * OTI, and which index set it accepts (one reading accepts indices 0 and 1; oti_rank = 2 is the
+ * nearest equivalent here), are undetermined.
+ * Every m <= 64 and every tau run one kernel (crp_otib.hip k_crp_otib); no row or column order
+ * statistic, no rolled copy of the reference and no distance plane is made.
+ * oti_rank outside 1 .. 12 under ACOSS_BIN_OTI, or an unknown binarize, returns ACOSS_E_ARG. */
+#define ACOSS_BIN_PERCENTILE 0
+#define ACOSS_BIN_OTI 1
+typedef struct acoss_crp_params2 {
+  acoss_crp_params base;
+  int32_t binarize;   /* ACOSS_BIN_PERCENTILE (what the entries without a 2 run) or ACOSS_BIN_OTI */
+  int32_t oti_rank;   /* ACOSS_BIN_OTI: 1 .. 12, Serra08's rule is 1; ignored under ACOSS_BIN_PERCENTILE */
+} acoss_crp_params2;
+
 /* Library / build information. */
 const char* acoss_version(void);
 const char* acoss_last_error(void);
@@ -224,6 +271,41 @@ int acoss_crp_rqa(const float* feats, const int64_t* track_off, const int32_t* t
  * 2^31 - 1 cells (a bin is an int32), returns ACOSS_E_SHAPE when a line measure is asked for. */
 int acoss_rqa_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t lmin, int64_t* counts_out, int32_t* lmax_out,
                   double* stats_out, float* smax_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream);
+
+/* The seven entries above that make a CRP from chroma, with the binarisation chosen by
+ * acoss_crp_params2 (the definition of ACOSS_BIN_OTI is at the struct). Each takes the arguments of
+ * the entry it is the twin of, gives its outputs under its conventions and refusals, and with
+ * binarize = ACOSS_BIN_PERCENTILE is that entry: the entries without a 2 widen their params with
+ * binarize = 0 and run the same driver, kernels and launches. Under ACOSS_BIN_OTI only the mask
+ * producer differs: the aligners, the tracing and direction DPs, the backtrack and the line walk
+ * consume its words unchanged.
+ * acoss_crp_pair2 under ACOSS_BIN_OTI: thr_row and thr_col must be NULL (ACOSS_E_ARG otherwise: there
+ * are no thresholds), dist is D_0, crp the mask of the batch kernel, and closer_out (may be NULL)
+ * receives closer(i, j) as (Mp x Np) uint8. Under ACOSS_BIN_PERCENTILE closer_out must be NULL. */
+int acoss_crp_align2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                     int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
+                     float* qmax_out, float* dmax_out, int32_t* oti_out, void* hip_stream);
+int acoss_crp_pair2(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params2* params,
+                    float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti, uint8_t* closer_out,
+                    void* hip_stream);
+int acoss_crp_locate2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                      int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
+                      float* qmax_out, int32_t* seg_out, int32_t* oti_out, void* hip_stream);
+int acoss_crp_locate_dmax2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                           int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
+                           float* dmax_out, int32_t* seg_out, int32_t* oti_out, void* hip_stream);
+int acoss_crp_path2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                    int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
+                    float* qmax_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
+                    int32_t* path_out, void* hip_stream);
+int acoss_crp_path_dmax2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                         int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
+                         float* dmax_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
+                         int32_t* path_out, void* hip_stream);
+int acoss_crp_rqa2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                   int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
+                   int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                   int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream);
 
 /* acoss smith_waterman_constrained (A8, acoss/algorithms/utils/alignment_tools.py:25-46) on
  * a batch of binary matrices: matrix b is (rows[b] x cols[b]) uint8 at byte offset off[b]
