@@ -121,6 +121,13 @@ for _name in ("acoss_crp_align", "acoss_crp_locate", "acoss_crp_locate_dmax", "a
     SIGNATURES[_name + "2"] = [ctypes.POINTER(CrpParams2) if a is ctypes.POINTER(CrpParams) else a
                                for a in SIGNATURES[_name]]
 SIGNATURES["acoss_crp_pair2"] = [_vp, _i32, _vp, _i32, ctypes.POINTER(CrpParams2), _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+# EarlyFusion's entries ending in 2: int32 binarize (EF_BINARIZE) directly after mu; acoss_earlyfusion_snf2
+# also gains binary_out before the stream
+for _name in ("acoss_earlyfusion", "acoss_earlyfusion_locate", "acoss_earlyfusion_path", "acoss_earlyfusion_snf"):
+    SIGNATURES[_name + "2"] = SIGNATURES[_name][:16] + [_i32] + SIGNATURES[_name][16:]
+SIGNATURES["acoss_earlyfusion_snf2"] = SIGNATURES["acoss_earlyfusion_snf2"][:-1] + [_vp, _vp]
+SIGNATURES["acoss_binarize_mutual"] = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_double, _i32, _vp, _vp]
+EF_BINARIZE = {"rows": 0, "mutual": 1}  # ACOSS_EF_BIN_ROWS, ACOSS_EF_BIN_MUTUAL
 
 _lib = None
 
@@ -661,6 +668,30 @@ def binarize_rows(D, nneighbs):
     return out
 
 
+def binarize_mutual(mats, kappa, mutual=True):
+    """The binarisation of EarlyFusion alone (acoss_binarize_mutual; "mutual" in include/acoss_hip.h)
+    for a list of float32 matrices: a list of uint8 device tensors of the same shapes, the mutual
+    rule, or the row rule csm_to_binary computes (mutual=False). It runs the batched pipeline's own
+    kernels; the largest row and column count of the list pick the shape class, as max_blocks does
+    there. Counts are clamped to the line lengths (no ValueError here)."""
+    binarize = check_ef_binarize(mutual)
+    if not kappa >= 0:
+        raise ValueError("kappa must be >= 0, got %r" % (kappa,))
+    torch = _torch()
+    mats = [_dev(m, torch.float32) for m in mats]
+    if any(m.dim() != 2 or m.shape[0] < 1 or m.shape[1] < 1 for m in mats):
+        raise ValueError("binarize_mutual takes non-empty 2-D matrices")
+    if not mats:
+        return []
+    flat, off, rows, cols, mr, mc = _pack_mats(mats, torch.float32)
+    out = torch.empty(flat.shape[0], dtype=torch.uint8, device="cuda")
+    rc = load_library().acoss_binarize_mutual(_ptr(flat), _ptr(off), _ptr(rows), _ptr(cols), len(mats), mr, mc,
+                                              float(kappa), binarize, _ptr(out), _stream())
+    _check(rc, "acoss_binarize_mutual")
+    offs = off.cpu().numpy()
+    return [out[int(o):int(o) + m.numel()].reshape(m.shape) for o, m in zip(offs, mats)]
+
+
 def wcsm(CSM, k1, k2, mu=0.5):
     """getWCSM (similarity_fusion.py:38-54)."""
     torch = _torch()
@@ -1011,20 +1042,37 @@ def simple_features(feats, track_off, track_len, win=200, skip=100, win_len_smoo
     return out[:total], out_off, T.astype(np.int32)
 
 
-def ef_neighbour_error(nb_query, nb_ref, kappa, K):
+def check_ef_binarize(mutual):
+    """The `mutual` flag every EarlyFusion layer takes (a bool; include/acoss_hip.h, "mutual") ->
+    ACOSS_EF_BIN_ROWS or ACOSS_EF_BIN_MUTUAL; ValueError for anything but a bool."""
+    if not isinstance(mutual, (bool, np.bool_)):
+        raise ValueError("mutual must be True or False, not %r" % (mutual,))
+    return EF_BINARIZE["mutual" if mutual else "rows"]
+
+
+def ef_mutual_suffix(mutual=False):
+    """What a cache or result name carries for the binarisation: '' for the row rule, '-mutual'."""
+    return "-mutual" if check_ef_binarize(mutual) else ""
+
+
+def ef_neighbour_error(nb_query, nb_ref, kappa, K, mutual=False):
     """The ValueError the reference raises for a pair of block counts, or None (host-only, no GPU).
     csm_to_binary takes argpartition(D, nn, 1) with nn = round(kappa * ncols) (kappa < 1) or kappa,
     which raises unless nn < ncols (cross_recurrence.py:150-156); getWCSM takes np.partition(CSM, K)
     along the columns and the rows, which raises unless K < ncols and K < nrows
-    (similarity_fusion.py:47-50). nb_query / nb_ref: block counts (arrays) of each pair's songs."""
+    (similarity_fusion.py:47-50). nb_query / nb_ref: block counts (arrays) of each pair's songs.
+    mutual: the column half takes the same count of the query's blocks (CSMToBinary(D.T) in Tralie's
+    CSMToBinaryMutual), so the same error for round(kappa * nrows) >= nrows."""
+    check_ef_binarize(mutual)
     nq = np.asarray(nb_query, np.int64)
     nr = np.asarray(nb_ref, np.int64)
     if kappa != 0:
-        nn = np.round(kappa * nr).astype(np.int64) if kappa < 1 else np.full(nr.shape, int(kappa), np.int64)
-        bad = np.flatnonzero(nn >= nr)
-        if len(bad):
-            b = bad[0]
-            return ValueError("kth(=%d) out of bounds (%d)" % (nn[b], nr[b]))
+        for n in (nr, nq) if mutual else (nr,):
+            nn = np.round(kappa * n).astype(np.int64) if kappa < 1 else np.full(n.shape, int(kappa), np.int64)
+            bad = np.flatnonzero(nn >= n)
+            if len(bad):
+                b = bad[0]
+                return ValueError("kth(=%d) out of bounds (%d)" % (nn[b], n[b]))
     bad = np.flatnonzero((K >= nr) | (K >= nq))
     if len(bad):
         b = bad[0]
@@ -1032,7 +1080,7 @@ def ef_neighbour_error(nb_query, nb_ref, kappa, K):
     return None
 
 
-def _check_ef_neighbours(bank, pairs, kappa, K):
+def _check_ef_neighbours(bank, pairs, kappa, K, mutual=False):
     """Reject pairs whose block counts the reference's argpartition / partition would refuse (see
     ef_neighbour_error) before the kernels run. The smallest counts decide: both conditions are
     monotone in the block count (n - round(kappa n) never decreases with n for kappa < 1)."""
@@ -1041,7 +1089,7 @@ def _check_ef_neighbours(bank, pairs, kappa, K):
     else:
         nbp = bank["nb"].long()[pairs.long()]
     lo_q, lo_r = int(nbp[:, 0].min()), int(nbp[:, 1].min())
-    err = ef_neighbour_error([lo_q], [lo_r], kappa, K)
+    err = ef_neighbour_error([lo_q], [lo_r], kappa, K, mutual)
     if err is not None:
         raise err
 
@@ -1072,11 +1120,13 @@ def _ef_band_order(pairs, T):
     return order[torch.argsort((runlen < band).to(torch.int8), stable=True)]
 
 
-def earlyfusion(bank, pairs, kappa=0.1, K=10, mu=0.5):
+def earlyfusion(bank, pairs, kappa=0.1, K=10, mu=0.5, mutual=False):
     """Batched EarlyFusion scores (earlyfusion_traile.py:157-198). bank: dict of device tensors
     'mfccs', 'ssms', 'chromas' (sum nb x d, float32), 'chroma_med' (T x 12), 'off' (T,) int64,
     'nb' (T,) int32 and host 'max_blocks'. Returns (P, 4) float64 device tensor with columns
-    mfccs, ssms, chromas, early."""
+    mfccs, ssms, chromas, early. mutual: binarise by mutual nearest neighbours (acoss_earlyfusion2
+    with ACOSS_EF_BIN_MUTUAL; include/acoss_hip.h) instead of the reference's row rule."""
+    binarize = check_ef_binarize(mutual)
     torch = _torch()
     lib = load_library()
     pairs, host = _pairs_dev(pairs, int(bank["nb"].shape[0]))
@@ -1084,17 +1134,21 @@ def earlyfusion(bank, pairs, kappa=0.1, K=10, mu=0.5):
     out = torch.empty((P, 4), dtype=torch.float64, device="cuda")
     if P == 0:
         return out
-    _check_ef_neighbours(bank, pairs if host is None or "nb_host" not in bank else host, kappa, K)
+    _check_ef_neighbours(bank, pairs if host is None or "nb_host" not in bank else host, kappa, K, mutual)
     T = int(bank["nb"].shape[0])
     order = _ef_band_order(pairs, T)
     if order is not None:
         pairs = pairs[order].contiguous()
     dst = out if order is None else torch.empty_like(out)
-    rc = lib.acoss_earlyfusion(_ptr(bank["mfccs"]), _ptr(bank["ssms"]), _ptr(bank["chromas"]), _ptr(bank["chroma_med"]),
-                               _ptr(bank["off"]), _ptr(bank["nb"]), T, int(bank["max_blocks"]),
-                               int(bank["mfccs"].shape[1]), int(bank["ssms"].shape[1]), int(bank["chromas"].shape[1]),
-                               _ptr(pairs), int(P), float(kappa), int(K), float(mu), _ptr(dst), _stream())
-    _check(rc, "acoss_earlyfusion")
+    lead = (_ptr(bank["mfccs"]), _ptr(bank["ssms"]), _ptr(bank["chromas"]), _ptr(bank["chroma_med"]),
+            _ptr(bank["off"]), _ptr(bank["nb"]), T, int(bank["max_blocks"]),
+            int(bank["mfccs"].shape[1]), int(bank["ssms"].shape[1]), int(bank["chromas"].shape[1]),
+            _ptr(pairs), int(P), float(kappa), int(K), float(mu))
+    if mutual:
+        rc = lib.acoss_earlyfusion2(*lead, binarize, _ptr(dst), _stream())
+    else:
+        rc = lib.acoss_earlyfusion(*lead, _ptr(dst), _stream())
+    _check(rc, "acoss_earlyfusion2" if mutual else "acoss_earlyfusion")
     if order is not None:
         out[order] = dst
     return out
@@ -1143,13 +1197,19 @@ def ef_snf_check_args(kappa, K, niters, reg_diag, max_blocks=None):
         raise ValueError("early SNF takes tracks of at most %d blocks, got %d" % (EF_SNF_MAX_BLOCKS, max_blocks))
 
 
-def earlyfusion_snf(bank, pairs, kappa, K, niters, reg_diag=1.0, want_cross=False, mu=0.5):
+def earlyfusion_snf(bank, pairs, kappa, K, niters, reg_diag=1.0, want_cross=False, mu=0.5, mutual=False,
+                    want_binary=False):
     """The per-pair similarity network fusion score of EarlyFusion (acoss_earlyfusion_snf; the
     definition is in include/acoss_hip.h). bank as earlyfusion() takes it. Returns a dict of device
     tensors: "score" f64 (P,), NaN for a pair the reference cannot fuse (ef_snf_pair_ok); with
     want_cross also "cross_off" i64 (P + 1,) and "cross" f64 (cross_off[-1],), pair p's M x N
     cross block of the fused matrix, row-major (both None otherwise). A kappa whose neighbour count
-    reaches a reference's block count raises the reference's ValueError, as earlyfusion() does."""
+    reaches a reference's block count raises the reference's ValueError, as earlyfusion() does.
+    mutual: the binary matrix keeps a cell only if it is also among the largest of its column
+    (acoss_earlyfusion_snf2; under it the same ValueError for a query's block count). want_binary:
+    also "binary" u8 (cross_off[-1],), pair p's M x N binary matrix as Smith-Waterman read it, at
+    cross_off[p] (all zero for a pair that cannot be fused), and "cross_off"."""
+    binarize = check_ef_binarize(mutual)
     ef_snf_check_args(kappa, K, niters, reg_diag, bank.get("max_blocks"))
     torch = _torch()
     lib = load_library()
@@ -1165,31 +1225,43 @@ def earlyfusion_snf(bank, pairs, kappa, K, niters, reg_diag=1.0, want_cross=Fals
         nn = int(np.round(kappa * lo)) if kappa < 1 else int(kappa)
         if nn >= lo:
             raise ValueError("kth(=%d) out of bounds (%d)" % (nn, lo))
-    off_d = cross = None
+        if mutual:
+            err = ef_neighbour_error([int(nb_host[host[:, 0]].min())], [lo], kappa, 0, True)
+            if err is not None:
+                raise err
+    off_d = cross = binary = None
     total = 0
-    if want_cross:
+    if want_cross or want_binary:
         off = ef_snf_cross_offsets(nb_host, host)
         total = int(off[-1])
         off_d = _dev(off, torch.int64)
-        cross = torch.empty(total, dtype=torch.float64, device="cuda")
+        if want_cross:
+            cross = torch.empty(total, dtype=torch.float64, device="cuda")
+        if want_binary:
+            binary = torch.zeros(total, dtype=torch.uint8, device="cuda")
     if P:
-        rc = lib.acoss_earlyfusion_snf(_ptr(bank["mfccs"]), _ptr(bank["ssms"]), _ptr(bank["chromas"]),
-                                       _ptr(bank["chroma_med"]), _ptr(bank["off"]), _ptr(bank["nb"]), T,
-                                       int(bank["max_blocks"]), int(bank["mfccs"].shape[1]),
-                                       int(bank["ssms"].shape[1]), int(bank["chromas"].shape[1]), _ptr(pairs), int(P),
-                                       float(kappa), int(K), float(mu), int(niters), float(reg_diag), _ptr(score),
-                                       _ptr(off_d), total, _ptr(cross) if total else None, _stream())
-        _check(rc, "acoss_earlyfusion_snf")
-    return {"score": score, "cross_off": off_d, "cross": cross}
+        lead = (_ptr(bank["mfccs"]), _ptr(bank["ssms"]), _ptr(bank["chromas"]), _ptr(bank["chroma_med"]),
+                _ptr(bank["off"]), _ptr(bank["nb"]), T, int(bank["max_blocks"]), int(bank["mfccs"].shape[1]),
+                int(bank["ssms"].shape[1]), int(bank["chromas"].shape[1]), _ptr(pairs), int(P), float(kappa), int(K),
+                float(mu))
+        tail = (int(niters), float(reg_diag), _ptr(score), _ptr(off_d), total,
+                _ptr(cross) if total and want_cross else None)
+        if mutual or want_binary:
+            rc = lib.acoss_earlyfusion_snf2(*lead, binarize, *tail, _ptr(binary) if total and want_binary else None,
+                                            _stream())
+        else:
+            rc = lib.acoss_earlyfusion_snf(*lead, *tail, _stream())
+        _check(rc, "acoss_earlyfusion_snf2" if mutual or want_binary else "acoss_earlyfusion_snf")
+    return {"score": score, "cross_off": off_d, "cross": cross, "binary": binary}
 
 
-def _ef_args(bank, pairs, kappa, K, mu):
+def _ef_args(bank, pairs, kappa, K, mu, mutual=False):
     """The arguments acoss_earlyfusion and its locate / path forms share, after earlyfusion()'s checks:
     (device pairs (P, 2) in the order they run in, that order (_ef_band_order) or None, the leading
     arguments up to the feature widths, the trailing kappa, K, mu)."""
     pairs, host = _pairs_dev(pairs, int(bank["nb"].shape[0]))
     if pairs.shape[0]:
-        _check_ef_neighbours(bank, pairs if host is None or "nb_host" not in bank else host, kappa, K)
+        _check_ef_neighbours(bank, pairs if host is None or "nb_host" not in bank else host, kappa, K, mutual)
     order = _ef_band_order(pairs, int(bank["nb"].shape[0]))
     if order is not None:
         pairs = pairs[order].contiguous()
@@ -1208,31 +1280,37 @@ def _unorder(order, t):
     return out
 
 
-def earlyfusion_locate(bank, pairs, kappa=0.1, K=10, mu=0.5):
+def earlyfusion_locate(bank, pairs, kappa=0.1, K=10, mu=0.5, mutual=False):
     """earlyfusion() with where each of the four alignments lies (acoss_earlyfusion_locate): device
     tensors {"scores" (P, 4) f64, earlyfusion()'s bit for bit, "seg" (P, 4, 4) i32}: seg[p, s] =
     (r0, c0, r1, c1), the first and last cell of the alignment in matrix s (mfccs, ssms, chromas,
     early) of pair p, rows the query's blocks and columns the reference's, (-1, -1, -1, -1) where
-    the score is 0."""
-    pairs, order, lead, tail = _ef_args(bank, pairs, kappa, K, mu)
+    the score is 0. mutual: as earlyfusion() (acoss_earlyfusion_locate2)."""
+    binarize = check_ef_binarize(mutual)
+    pairs, order, lead, tail = _ef_args(bank, pairs, kappa, K, mu, mutual)
     P = pairs.shape[0]
     scores, seg = _empty("float64", P, 4), _empty("int32", P, 4, 4)
-    if P:
+    if P and mutual:
+        rc = load_library().acoss_earlyfusion_locate2(*lead, _ptr(pairs), int(P), *tail, binarize, _ptr(scores),
+                                                      _ptr(seg), _stream())
+        _check(rc, "acoss_earlyfusion_locate2")
+    elif P:
         rc = load_library().acoss_earlyfusion_locate(*lead, _ptr(pairs), int(P), *tail, _ptr(scores), _ptr(seg),
                                                      _stream())
         _check(rc, "acoss_earlyfusion_locate")
     return {"scores": _unorder(order, scores), "seg": _unorder(order, seg)}
 
 
-def earlyfusion_path(bank, pairs, kappa=0.1, K=10, mu=0.5):
+def earlyfusion_path(bank, pairs, kappa=0.1, K=10, mu=0.5, mutual=False):
     """earlyfusion_locate with the four whole paths of every pair (acoss_earlyfusion_path): {"scores",
     "seg", "path_off" (4 P + 1,) i64, "cells" (total, 2) i32}; the path of matrix s of pair p is
     cells[path_off[4 p + s]:path_off[4 p + s + 1]], (query block, reference block) cells in steps
     (1, 1), (2, 1), (1, 2). The pairs go to the library in chunks whose padded output stays near
-    PATH_CHUNK_BYTES; each is compacted on the device."""
+    PATH_CHUNK_BYTES; each is compacted on the device. mutual: as earlyfusion() (acoss_earlyfusion_path2)."""
+    binarize = check_ef_binarize(mutual)
     torch = _torch()
     lib = load_library()
-    pairs, order, lead, tail = _ef_args(bank, pairs, kappa, K, mu)
+    pairs, order, lead, tail = _ef_args(bank, pairs, kappa, K, mu, mutual)
     P = pairs.shape[0]
     scores, seg, lens = _empty("float64", P, 4), _empty("int32", P, 4, 4), _empty("int32", P, 4)
     cap = max(1, sw_path_bound(int(bank["max_blocks"]), int(bank["max_blocks"])))
@@ -1241,9 +1319,12 @@ def earlyfusion_path(bank, pairs, kappa=0.1, K=10, mu=0.5):
     for a in range(0, P, chunk):
         n = min(chunk, P - a)
         padded = torch.empty((4 * n, cap, 2), dtype=torch.int32, device="cuda")
-        rc = lib.acoss_earlyfusion_path(*lead, _ptr(pairs[a:a + n]), int(n), *tail, _ptr(scores[a:a + n]),
-                                        _ptr(seg[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded), _stream())
-        _check(rc, "acoss_earlyfusion_path")
+        out_args = (_ptr(scores[a:a + n]), _ptr(seg[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded), _stream())
+        if mutual:
+            rc = lib.acoss_earlyfusion_path2(*lead, _ptr(pairs[a:a + n]), int(n), *tail, binarize, *out_args)
+        else:
+            rc = lib.acoss_earlyfusion_path(*lead, _ptr(pairs[a:a + n]), int(n), *tail, *out_args)
+        _check(rc, "acoss_earlyfusion_path2" if mutual else "acoss_earlyfusion_path")
         parts.append(_compact_paths(lens[a:a + n].reshape(-1), padded)[1])
     cells = torch.cat(parts) if parts else torch.empty((0, 2), dtype=torch.int32, device="cuda")
     run_off = torch.zeros(4 * P + 1, dtype=torch.int64, device="cuda")  # in the order the pairs ran in

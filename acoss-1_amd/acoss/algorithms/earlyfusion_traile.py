@@ -56,9 +56,21 @@ class EarlyFusion(CoverAlgorithm):
     _Ds_on_every_rank = True
     _takes_candidates = False  # the fusion needs every pair's score
 
+    @classmethod
+    def algorithm_name(cls, mutual=False):
+        """The name of the Ds cache and the results: 'EarlyFusionTraile' (the reference's row rule),
+        'EarlyFusionTraile-mutual' under the mutual nearest-neighbour binarisation."""
+        return "EarlyFusionTraile" + _lib.ef_mutual_suffix(mutual)
+
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='Covers80', blocksize=20,
                  mfccs_per_block=50, ssm_res=50, chromas_per_block=40, kappa=0.1, K=10, niters=5, log_times=False,
-                 cachedir="cache", early_snf=False):
+                 cachedir="cache", mutual=False, early_snf=False):
+        """mutual=True: every binary matrix of this object (similarity, localize, align_path,
+        pair_matrices, pair_fusion, the early_snf score) keeps a cell only if it is among the
+        nearest neighbours of its row AND of its column (Tralie 2017; include/acoss_hip.h, "mutual")
+        instead of the reference's row rule."""
+        name = self.algorithm_name(mutual)
+        self.mutual = bool(mutual)
         self.chroma_type = chroma_type
         self.blocksize = blocksize
         self.mfccs_per_block = mfccs_per_block
@@ -77,7 +89,7 @@ class EarlyFusion(CoverAlgorithm):
             self.times = {'features': [], 'raw': []}
         self._dev = {}
         self._pending = []  # background cache writes (flush_cache)
-        CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name="EarlyFusionTraile", datapath=datapath,
+        CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name=name, datapath=datapath,
                                 shortname=shortname,
                                 similarity_types=["mfccs", "ssms", "chromas", "early"] +
                                 (["early_snf"] if self.early_snf else []), cachedir=cachedir)
@@ -85,10 +97,14 @@ class EarlyFusion(CoverAlgorithm):
     def get_cacheprefix(self):
         return "%s/%s_%s_%s" % (self.cachedir, self.name, self.shortname, self.chroma_type)
 
+    def _block_cacheprefix(self):
+        """The per-song block-feature files: they do not depend on `mutual`, so both share them."""
+        return "%s/%s_%s_%s" % (self.cachedir, self.algorithm_name(), self.shortname, self.chroma_type)
+
     def load_features(self, i, do_plot=False):
         """Blocked features of song i: 'mfccs', 'ssms', 'chromas', 'chroma_med' (:67-154),
         cached in memory and on disk ('<prefix>_<i>.npz'); computed on the GPU."""
-        filepath = "%s_%i.h5" % (self.get_cacheprefix(), i)
+        filepath = "%s_%i.h5" % (self._block_cacheprefix(), i)
         if i in self.all_block_feats:
             return self.all_block_feats[i]
         try:
@@ -126,7 +142,7 @@ class EarlyFusion(CoverAlgorithm):
             self.all_block_feats[i] = bf
             if write_cache:  # on a background thread: ~1 ms of np.savez per song (15 s at 15,000 songs)
                 self._pending.append(self._cache_writer().submit(
-                    _save_feature_file, "%s_%i.h5" % (self.get_cacheprefix(), i), bf))
+                    _save_feature_file, "%s_%i.h5" % (self._block_cacheprefix(), i), bf))
             res.append(bf)
         if self.log_times:
             self.times['features'].append((time.time() - tic) / max(1, len(idx)))
@@ -194,7 +210,8 @@ class EarlyFusion(CoverAlgorithm):
 
     def pair_matrices(self, i, j):
         """The four binary matrices of pair (i, j) (device uint8), in score order
-        mfccs, ssms, chromas, early (:157-189)."""
+        mfccs, ssms, chromas, early (:157-189); under `mutual` the mutual masks (the batched
+        pipeline's row launch and column pass, through acoss_binarize_mutual)."""
         torch = _lib._torch()
         a, b = self._device(i), self._device(j)
         csms = {}
@@ -204,12 +221,16 @@ class EarlyFusion(CoverAlgorithm):
         csms['chromas'] = _lib.csm(a['chromas'], b['chromas'], kind="cosine", oti_shift=oti)
         ncols = csms['mfccs'].shape[1]
         nn = nneighbs(self.kappa, ncols)
-        mats = [_lib.binarize_rows(csms[s], nn) for s in ('mfccs', 'ssms', 'chromas')]
         wsum = torch.zeros_like(csms['mfccs'])
         for s in ('mfccs', 'ssms', 'chromas'):
             wsum += _lib.wcsm(csms[s], self.K, self.K, 0.5)
-        mats.append(_lib.binarize_rows(_lib.neg_exp(wsum), nn))
-        return mats
+        four = [csms[s] for s in ('mfccs', 'ssms', 'chromas')] + [_lib.neg_exp(wsum)]
+        if self.mutual:
+            err = _lib.ef_neighbour_error([four[0].shape[0]], [ncols], self.kappa, self.K, True)
+            if err is not None:
+                raise err
+            return _lib.binarize_mutual(four, self.kappa)
+        return [_lib.binarize_rows(D, nn) for D in four]
 
     def _bank(self):
         """All tracks' block features packed once into HBM for the batched kernels."""
@@ -237,13 +258,15 @@ class EarlyFusion(CoverAlgorithm):
         if len(idxs) == 0:
             return
         tic = time.time()
-        scores = _lib.earlyfusion(self._bank(), idxs.astype(np.int32), self.kappa, self.K).cpu().numpy()
+        scores = _lib.earlyfusion(self._bank(), idxs.astype(np.int32), self.kappa, self.K,
+                                  mutual=self.mutual).cpu().numpy()
         if self.log_times:
             self.times['raw'].append((time.time() - tic) / len(idxs))
         for s, key in enumerate(("mfccs", "ssms", "chromas", "early")):
             self.Ds[key][idxs[:, 0], idxs[:, 1]] = scores[:, s]
         if self.early_snf:
-            snf = _lib.earlyfusion_snf(self._bank(), idxs.astype(np.int32), self.kappa, self.K, self.niters)
+            snf = _lib.earlyfusion_snf(self._bank(), idxs.astype(np.int32), self.kappa, self.K, self.niters,
+                                       mutual=self.mutual)
             self.Ds["early_snf"][idxs[:, 0], idxs[:, 1]] = snf["score"].cpu().numpy()
 
     def _device_scores(self, idxs):
@@ -252,32 +275,27 @@ class EarlyFusion(CoverAlgorithm):
         across ranks (algorithm_template._device_all_pairwise)."""
         idxs = np.asarray(idxs)
         tic = time.time()
-        sc = _lib.earlyfusion(self._bank(), idxs.astype(np.int32), self.kappa, self.K)
+        sc = _lib.earlyfusion(self._bank(), idxs.astype(np.int32), self.kappa, self.K, mutual=self.mutual)
         if self.log_times:
             self.times['raw'].append((time.time() - tic) / max(1, len(idxs)))
         out = {key: sc[:, s].float() for s, key in enumerate(("mfccs", "ssms", "chromas", "early"))}
         if self.early_snf:
             out["early_snf"] = _lib.earlyfusion_snf(self._bank(), idxs.astype(np.int32), self.kappa, self.K,
-                                                    self.niters)["score"].float()
+                                                    self.niters, mutual=self.mutual)["score"].float()
         return out
 
     def pair_fusion(self, i, j):
         """(cross, binary) of pair (i, j): the M x N cross block F[:M, M:] + F[M:, :M].T of the pair's
         fused matrix (host float64; NaN where the reference cannot fuse the pair) and the binary
-        matrix the early_snf score aligns (host uint8: round(kappa N) ones per row at the largest
-        values, ties to the lowest column). Beside pair_matrices, for the plots of the reference's
-        do_plot branch (:184-196)."""
+        matrix the early_snf score aligns, as the device wrote it (host uint8: round(kappa N) ones per
+        row at the largest values, ties to the lowest column; under `mutual` only those also among
+        the round(kappa M) largest of their column; all zero where the pair cannot be fused). Beside
+        pair_matrices, for the plots of the reference's do_plot branch (:184-196)."""
         r = _lib.earlyfusion_snf(self._bank(), np.array([[i, j]], np.int32), self.kappa, self.K, self.niters,
-                                 want_cross=True)
+                                 want_cross=True, mutual=self.mutual, want_binary=True)
         nb = self._bank()["nb_host"]
-        cross = r["cross"].cpu().numpy().reshape(int(nb[i]), int(nb[j]))
-        binary = np.zeros(cross.shape, np.uint8)
-        if self.kappa == 0:
-            binary[:] = 1
-        elif not np.isnan(cross).any():
-            idx = np.argsort(-cross, axis=1, kind="stable")[:, :nneighbs(self.kappa, cross.shape[1])]
-            np.put_along_axis(binary, idx, 1, 1)
-        return cross, binary
+        shape = (int(nb[i]), int(nb[j]))
+        return r["cross"].cpu().numpy().reshape(shape), r["binary"].cpu().numpy().reshape(shape)
 
     def _onsets(self, songs):
         """{song: (beat onsets int64, chroma frame count)} read from the songs' feature files; the
@@ -307,7 +325,7 @@ class EarlyFusion(CoverAlgorithm):
         read from their feature files on demand; a ValueError names a song whose file has none.
         Not collective: a rank localises the pairs it is given."""
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = _lib.earlyfusion_locate(self._bank(), idxs, self.kappa, self.K)
+        r = _lib.earlyfusion_locate(self._bank(), idxs, self.kappa, self.K, mutual=self.mutual)
         cells = r["seg"].cpu().numpy()
         out = {"scores": r["scores"].cpu().numpy(), "cells": cells}
         none = cells[:, :, 0] < 0
@@ -334,7 +352,7 @@ class EarlyFusion(CoverAlgorithm):
         (query block, reference block) from cells[p, s, :2] to cells[p, s, 2:], each step (1, 1),
         (2, 1) or (1, 2); empty where the score is 0. Not collective."""
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = _lib.earlyfusion_path(self._bank(), idxs, self.kappa, self.K)
+        r = _lib.earlyfusion_path(self._bank(), idxs, self.kappa, self.K, mutual=self.mutual)
         return {"scores": r["scores"].cpu().numpy(), "cells": r["seg"].cpu().numpy(),
                 "path_off": r["path_off"].cpu().numpy(), "path_cells": r["cells"].cpu().numpy()}
 
@@ -352,7 +370,7 @@ class EarlyFusion(CoverAlgorithm):
         if not self._prepared:
             from ..features_io import cache_readable, load_many
             todo = [i for i in range(self.N) if i not in self.all_block_feats]
-            paths = {i: "%s_%i.h5" % (self.get_cacheprefix(), i) for i in todo}
+            paths = {i: "%s_%i.h5" % (self._block_cacheprefix(), i) for i in todo}
             have = [i for i in todo if cache_readable(paths[i])]
             if have:
                 for i, bf in zip(have, load_many([paths[i] for i in have])):

@@ -8,7 +8,7 @@ import numpy as np
 from ... import _lib
 
 __all__ = ["get_ssm", "get_csm", "get_csm_euclidean", "get_csm_cosine", "get_oti", "get_csm_blocked_oti",
-           "csm_to_binary", "nneighbs"]
+           "csm_to_binary", "csm_to_binary_mutual", "nneighbs"]
 
 
 def _host(t):
@@ -68,3 +68,21 @@ def csm_to_binary(D, kappa):
     if nn >= D.shape[1]:
         raise ValueError("kth(=%d) out of bounds (%d)" % (nn, D.shape[1]))  # np.argpartition's error
     return _host(_lib.binarize_rows(np.asarray(D, np.float32), nn))
+
+
+def csm_to_binary_mutual(D, kappa):
+    """Binarisation by MUTUAL nearest neighbours (Tralie 2017; the author's CSMToBinaryMutual =
+    CSMToBinary(D) * CSMToBinary(D.T).T; the definition: include/acoss_hip.h, "mutual"): a cell is 1
+    when it is among the round(kappa * ncols) smallest of its row (ties: lowest column) AND among
+    the round(kappa * nrows) smallest of its column (ties: lowest row). numpy in, uint8 out;
+    kappa == 0 -> all ones; raises csm_to_binary's ValueError on either axis."""
+    D = np.asarray(D)
+    if D.ndim != 2:
+        raise ValueError("csm_to_binary_mutual takes a 2-D matrix")
+    if kappa == 0:
+        return np.ones(D.shape, np.uint8)
+    for n in (D.shape[1], D.shape[0]):
+        nn = nneighbs(kappa, n)
+        if nn >= n:
+            raise ValueError("kth(=%d) out of bounds (%d)" % (nn, n))  # np.argpartition's error
+    return _host(_lib.binarize_mutual([np.asarray(D, np.float32)], kappa)[0])

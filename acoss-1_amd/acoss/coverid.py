@@ -22,11 +22,12 @@ _LOG_FILE_PATH = "acoss.coverid.log"
 algorithm_names = ["Serra09", "EarlyFusionTraile", "LateFusionChen", "FTM2D", "SiMPle"]
 shortlist_algorithms = ("Serra09", "SiMPle")  # the alignment scorers that take an FTM2D shortlist
 binarize_algorithms = ("Serra09", "LateFusionChen")  # the scorers on a CRP, which take its binarisation
+mutual_algorithms = ("EarlyFusionTraile", "EarlyFusion")  # the mutual nearest-neighbour binarisation
 
 
 def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09", shortname="covers80",
               parallel=True, n_workers=-1, cachedir="cache", shortlist=None, measure="qmax", binarize="percentile",
-              oti_rank=1):
+              oti_rank=1, mutual=False):
     """Run one cover-ID algorithm over a dataset CSV and print/write its evaluation statistics.
     Returns the algorithm object (its Ds hold the similarity matrices).
     shortlist: None, or k: Serra09 / SiMPle score only each song's k best FTM2D candidates (shingles
@@ -36,7 +37,9 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
     'det', 'lmean', 'entr', 'rr'); any other than 'qmax' runs, caches and reports as 'Serra09-<measure>'.
     binarize, oti_rank: Serra09 / LateFusionChen on the OTI-binary CRP of Serra08 (binarize='oti', oti_rank in
     1 .. 12; include/acoss_hip.h, acoss_crp_params2) in place of the percentile CRP; they run, cache and report
-    as 'Serra09-otib', 'LateFusionChen-otib', with the rank appended above 1."""
+    as 'Serra09-otib', 'LateFusionChen-otib', with the rank appended above 1.
+    mutual: EarlyFusionTraile binarises by mutual nearest neighbours (Tralie 2017; include/acoss_hip.h,
+    "mutual") in place of the reference's row rule; it runs, caches and reports as 'EarlyFusionTraile-mutual'."""
     logger = log(_LOG_FILE_PATH)
     if algorithm not in algorithm_names and algorithm != "EarlyFusion":
         warn = ("acoss.coverid: Couldn't find '%s' algorithm in acoss Available cover id algorithms are %s "
@@ -53,6 +56,9 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
     if (binarize != "percentile" or oti_rank != 1) and algorithm not in binarize_algorithms:
         raise ValueError("binarize and oti_rank are supported by %s only, not by '%s'"
                          % (" and ".join(binarize_algorithms), algorithm))
+    from ._lib import check_ef_binarize
+    if check_ef_binarize(mutual) and algorithm not in mutual_algorithms:
+        raise ValueError("mutual is supported by EarlyFusionTraile only, not by '%s'" % algorithm)
     logger.info("Running acoss cover identification benchmarking for the algorithm - '%s'" % algorithm)
     start = time.monotonic()
     kw = dict(dataset_csv=dataset_csv, datapath=feature_dir, chroma_type=feature_type, shortname=shortname,
@@ -75,7 +81,7 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         algo.normalize_by_length()
     elif algorithm in ("EarlyFusionTraile", "EarlyFusion"):
         from .algorithms.earlyfusion_traile import EarlyFusion
-        algo = EarlyFusion(**kw)
+        algo = EarlyFusion(mutual=mutual, **kw)
         # the reference's load_features(i) loop (coverid.py:80-81): the same per-song caches and clique
         # bookkeeping, with the uncached songs' block features made ceil(N / 256) launches at a time
         algo.prepare()
@@ -135,6 +141,8 @@ def parser_args(cmd_args):
     parser.add_argument('--oti-rank', type=int, action="store", default=1,
                         help="with --binarize oti: a cell is a hit when fewer than this many further "
                              "transpositions are closer (1 .. 12)")
+    parser.add_argument('--mutual', action="store_true",
+                        help="EarlyFusionTraile: binarise by mutual nearest neighbours (rows and columns)")
     return parser.parse_args(cmd_args)
 
 
@@ -142,4 +150,4 @@ if __name__ == '__main__':
     args = parser_args(sys.argv[1:])
     benchmark(dataset_csv=args.dataset_csv, feature_dir=args.feature_dir, feature_type=args.chroma_type,
               algorithm=args.method, shortname=args.shortname, parallel=bool(args.parallel), n_workers=args.n_workers,
-              shortlist=args.shortlist, binarize=args.binarize, oti_rank=args.oti_rank)
+              shortlist=args.shortlist, binarize=args.binarize, oti_rank=args.oti_rank, mutual=args.mutual)

@@ -17,7 +17,9 @@
 //                 column, into u16 bit words of 16 rows (the SW input). Tracks of at most 64 blocks
 //                 and nn <= 8: k_ef_binarize_lanes, a wave per (pair, matrix) with a row per lane;
 //                 at most 64 blocks otherwise: k_ef_binarize_small, a block per (pair, matrix);
-//                 longer tracks: k_ef_binarize, a wave per row (knockout rounds or a radix select)
+//                 longer tracks: k_ef_binarize, a wave per row (knockout rounds or a radix select);
+//                 ef_launch_rowbin picks among them. Under ACOSS_EF_BIN_MUTUAL (the entries ending
+//                 in 2) the column pass of ef_mutual.hip then clears what the columns do not keep
 //   k_ef_kmin*    mean of the K smallest of each row (k_ef_kmin_rows, a wave per 64 rows through
 //                 LDS tiles) and column (k_ef_kmin, a thread per column), K <= 16; k_ef_kmean, a
 //                 wave-per-line select, beyond that
@@ -34,6 +36,7 @@
 
 #include "common.hpp"
 #include "ef_internal.hpp"
+#include "ef_select.hpp"
 #include "sw_internal.hpp"
 
 namespace acoss {
@@ -52,66 +55,6 @@ __device__ __forceinline__ unsigned fkey(float f) {
 // takes 16 rows (one wave per row) and writes them as one row of u16 bit words (bit r = row
 // 16g + r) in LDS, then to the pair's bit plane for SW. blockIdx.z = CSM plane, written to
 // bit plane z + plane0 of the pair (plane stride = wplane words, 4 planes per pair).
-// The nn-th smallest (1-based) of the wave's keys kr (KB per lane) within [lo, hi], by radix
-// select: from the highest bit where lo and hi differ, 8-bit digits, each digit from one LDS
-// histogram of the candidates (keys matching the digits so far) and one wave scan of its 256
-// bins; about 4 passes instead of the ~26 count passes of a bisection over [lo, hi]. Every key
-// issues one unconditional ds_add: candidates to their digit's bin, the rest to a lane-private
-// sink word (hist: 256 bins + 64 sink words, this wave's own). Same answer as the bisection:
-// the least key v with #(keys <= v) >= nn.
-template <int KB>
-__device__ __forceinline__ unsigned radix_kth(const unsigned (&kr)[KB], unsigned lo, unsigned hi, int nn, int lane,
-                                              unsigned* hist) {
-  if (lo >= hi) return lo;
-  typedef __attribute__((address_space(3))) unsigned lds_u32;
-  const unsigned hb = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(lds_u32*)hist);
-  const unsigned sk = hb + 1024u + 4u * (unsigned)lane;
-  int sh = 32 - __builtin_clz(lo ^ hi);  // bits [0, sh) differ inside [lo, hi]
-  unsigned prefix = sh >= 32 ? 0u : (lo >> sh) << sh;
-  int rank = nn - 1;
-  while (sh > 0) {  // wave-uniform
-    const int dsh = sh > 8 ? sh - 8 : 0;
-    reinterpret_cast<uint4*>(hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
-    __builtin_amdgcn_wave_barrier();
-    const unsigned P = sh >= 32 ? 0u : prefix >> sh;
-#pragma unroll
-    for (int q = 0; q < KB; ++q) {
-      const unsigned k = kr[q];
-      const bool cand = sh >= 32 || (k >> sh) == P;
-      const unsigned d = (k >> dsh) & 0xffu;
-      const unsigned a = cand ? hb + 4u * d : sk;
-      __hip_atomic_fetch_add((lds_u32*)(size_t)a, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    }
-    __builtin_amdgcn_wave_barrier();
-    const uint4 hv = reinterpret_cast<const uint4*>(hist)[lane];  // bins 4 lane .. 4 lane + 3
-    const int sl = (int)(hv.x + hv.y + hv.z + hv.w);
-    const int S = wave_incl_scan(sl);
-    const int E = S - sl;
-    const int src = __builtin_ctzll(__ballot(E <= rank && rank < S));
-    int r = rank - __builtin_amdgcn_readlane(E, src);
-    const int h0 = __builtin_amdgcn_readlane((int)hv.x, src), h1 = __builtin_amdgcn_readlane((int)hv.y, src),
-              h2 = __builtin_amdgcn_readlane((int)hv.z, src);
-    unsigned b = 0;
-    if (r >= h0) {
-      r -= h0;
-      b = 1;
-      if (r >= h1) {
-        r -= h1;
-        b = 2;
-        if (r >= h2) {
-          r -= h2;
-          b = 3;
-        }
-      }
-    }
-    prefix |= (4u * (unsigned)src + b) << dsh;
-    rank = r;
-    sh = dsh;
-    __builtin_amdgcn_wave_barrier();
-  }
-  return prefix;
-}
-
 template <int KB>  // keys per lane held in registers (rows of up to 64 * KB columns)
 __device__ __forceinline__ void ef_binarize_row(const float* __restrict__ x, int N, double kappa, int lane,
                                                 unsigned* bits, unsigned bit, unsigned* hist) {
@@ -503,6 +446,29 @@ int ef_launch_swmeta(const EfPairs& E, int P, int repeat, int32_t* rows, int32_t
   return ACOSS_OK;
 }
 
+int ef_launch_rowbin(const float* C, int64_t mstride, int ld, const EfPairs& E, int P, double kappa, uint16_t* Wb,
+                     int64_t wplane, int plane0, int nplanes, hipStream_t st) {
+  // one binarize block per (pair, matrix) when every track has at most 64 blocks (15,000 Da-TACOS-
+  // shape songs: 4.04M -> 4.38M pairs/s, profiles/r05/ef_short/efbin15k_*.log)
+  const bool small_bin = ld <= 64;
+  // ... and one wave per (pair, matrix) with a row per lane when every row's nn is small (the nn
+  // rounds cost nn passes over the row's registers); ACOSS_EF_LANEBIN=0 keeps k_ef_binarize_small
+  const int nn_max = kappa < 1.0 ? (int)rint(kappa * 64.0) : (int)kappa;
+  static const bool lanebin_env = !(getenv("ACOSS_EF_LANEBIN") && getenv("ACOSS_EF_LANEBIN")[0] == '0');
+  const bool lane_bin = small_bin && lanebin_env && nn_max <= 8;
+  if (lane_bin)
+    hipLaunchKernelGGL(k_ef_binarize_lanes, dim3((unsigned)((nplanes * P + 3) / 4)), dim3(256), 0, st, C, mstride, ld,
+                       E, kappa, Wb, wplane, plane0, nplanes, nplanes * P);
+  else if (small_bin)
+    hipLaunchKernelGGL(k_ef_binarize_small, dim3(P, nplanes), dim3(256), 0, st, C, mstride, ld, E, kappa, Wb, wplane,
+                       plane0);
+  else  // k_ef_binarize keeps one u32 per column in LDS
+    hipLaunchKernelGGL(k_ef_binarize, dim3((ld + 15) / 16, P, nplanes), dim3(1024), (size_t)ld * 4, st, C, mstride, ld,
+                       E, kappa, Wb, wplane, plane0);
+  ACOSS_LAUNCH_CHECK();
+  return ACOSS_OK;
+}
+
 namespace {
 
 // What the batch driver does with a chunk's 4P bit planes, its last stage.
@@ -515,9 +481,14 @@ enum EfStage { EF_SCORE, EF_LOCATE, EF_PATH };
 int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float* ssm, const float* chroma,
                const float* chroma_med, const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
                int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs,
-               int64_t n_pairs, double kappa, int32_t K, float mu, double* scores_out, int32_t* seg_out,
-               int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+               int64_t n_pairs, double kappa, int32_t K, float mu, int32_t binarize, double* scores_out,
+               int32_t* seg_out, int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
   clear_error();
+  if (binarize != ACOSS_EF_BIN_ROWS && binarize != ACOSS_EF_BIN_MUTUAL) {
+    set_error("%s: unknown binarize %d", entry, binarize);
+    return ACOSS_E_ARG;
+  }
+  const bool mutual = binarize == ACOSS_EF_BIN_MUTUAL;
   const EfBank B{mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, d_mfcc, d_ssm, d_chroma};
   if (int rc = ef_check_args(entry, B, max_blocks, pairs, n_pairs, kappa, K, max_blocks, scores_out,
                              n_pairs > 0 && ((stage == EF_LOCATE && !seg_out) ||
@@ -600,17 +571,8 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
     ACOSS_HIP_CHECK(hipEventRecord(e0, s));
     ACOSS_HIP_CHECK(hipStreamWaitEvent(ss[1], e0, 0));
   }
-  const size_t bin_lds = (size_t)ld * 4;
   const int64_t mstride = (int64_t)mat * chunk;       // between the 3 CSM planes
   const int64_t meanstride = (int64_t)ld * chunk;     // between the 3 mean vectors
-  // one binarize block per (pair, matrix) when every track has at most 64 blocks (15,000 Da-TACOS-
-  // shape songs: 4.04M -> 4.38M pairs/s, profiles/r05/ef_short/efbin15k_*.log)
-  const bool small_bin = ld <= 64;
-  // ... and one wave per (pair, matrix) with a row per lane when every row's nn is small (the nn
-  // rounds cost nn passes over the row's registers); ACOSS_EF_LANEBIN=0 keeps k_ef_binarize_small
-  const int nn_max = kappa < 1.0 ? (int)rint(kappa * 64.0) : (int)kappa;
-  static const bool lanebin_env = !(getenv("ACOSS_EF_LANEBIN") && getenv("ACOSS_EF_LANEBIN")[0] == '0');
-  const bool lane_bin = small_bin && lanebin_env && nn_max <= 8;
   // column k-smallest means: 4 pairs per 256-thread block when every track has at most 64 blocks
   const int kmin_ppb = ld <= 64 ? 4 : 1;
   const unsigned kmin_gx = ld <= 64 ? 1u : (unsigned)((ld + 255) / 256);
@@ -629,15 +591,9 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
     int* oti = sets[ci & (nset - 1)].oti;
     if (int rc = ef_launch_csms(B, R, pairs + 2 * p0, P, ld, oti, false, C, mstride, st)) return rc;
     prof_begin(PH_BIN, st);
-    if (lane_bin)
-      hipLaunchKernelGGL(k_ef_binarize_lanes, dim3((unsigned)((3 * P + 3) / 4)), dim3(256), 0, st, C, mstride, ld, E,
-                         kappa, Wb, wplane, 0, 3, 3 * P);
-    else if (small_bin)
-      hipLaunchKernelGGL(k_ef_binarize_small, dim3(P, 3), dim3(256), 0, st, C, mstride, ld, E, kappa, Wb, wplane, 0);
-    else
-      hipLaunchKernelGGL(k_ef_binarize, dim3((ld + 15) / 16, P, 3), dim3(1024), bin_lds, st, C, mstride, ld, E, kappa,
-                         Wb, wplane, 0);
-    ACOSS_LAUNCH_CHECK();
+    if (int rc = ef_launch_rowbin(C, mstride, ld, E, P, kappa, Wb, wplane, 0, 3, st)) return rc;
+    if (mutual)  // before k_ef_wsum writes the early matrix over the first CSM
+      if (int rc = ef_launch_colpass(C, mstride, ld, E, P, kappa, Wb, wplane, 0, 3, st)) return rc;
     prof_end(PH_BIN, st);
     prof_begin(PH_WCSM, st);
     if (K == 10) {  // EarlyFusion's K: the k-th smallest is a fixed register, no per-element select
@@ -667,15 +623,9 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
     ACOSS_LAUNCH_CHECK();
     prof_end(PH_WCSM, st);
     prof_begin(PH_BIN, st);
-    if (lane_bin)
-      hipLaunchKernelGGL(k_ef_binarize_lanes, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, C, mstride, ld, E, kappa,
-                         Wb, wplane, 3, 1, P);
-    else if (small_bin)
-      hipLaunchKernelGGL(k_ef_binarize_small, dim3(P, 1), dim3(256), 0, st, C, mstride, ld, E, kappa, Wb, wplane, 3);
-    else
-      hipLaunchKernelGGL(k_ef_binarize, dim3((ld + 15) / 16, P, 1), dim3(1024), bin_lds, st, C, mstride, ld, E, kappa,
-                         Wb, wplane, 3);
-    ACOSS_LAUNCH_CHECK();
+    if (int rc = ef_launch_rowbin(C, mstride, ld, E, P, kappa, Wb, wplane, 3, 1, st)) return rc;
+    if (mutual)
+      if (int rc = ef_launch_colpass(C, mstride, ld, E, P, kappa, Wb, wplane, 3, 1, st)) return rc;
     prof_end(PH_BIN, st);
     prof_begin(PH_SW, st);
     int rc = ef_launch_swmeta(E, P, 4, m_rows, m_cols, st);
@@ -706,14 +656,34 @@ int ef_batches(EfStage stage, const char* entry, const float* mfcc, const float*
 
 using namespace acoss;
 
+extern "C" int acoss_earlyfusion2(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                                  const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
+                                  int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma,
+                                  const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K, float mu,
+                                  int32_t binarize, double* scores_out, void* hip_stream) {
+  return ef_batches(EF_SCORE, "acoss_earlyfusion", mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks,
+                    max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, binarize, scores_out, nullptr, 0,
+                    nullptr, nullptr, hip_stream);
+}
+
 extern "C" int acoss_earlyfusion(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
                                  const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
                                  int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma,
                                  const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K, float mu,
                                  double* scores_out, void* hip_stream) {
-  return ef_batches(EF_SCORE, "acoss_earlyfusion", mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks,
-                    max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, scores_out, nullptr, 0, nullptr,
-                    nullptr, hip_stream);
+  return acoss_earlyfusion2(mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, max_blocks, d_mfcc, d_ssm,
+                            d_chroma, pairs, n_pairs, kappa, K, mu, ACOSS_EF_BIN_ROWS, scores_out, hip_stream);
+}
+
+extern "C" int acoss_earlyfusion_locate2(const float* mfcc, const float* ssm, const float* chroma,
+                                         const float* chroma_med, const int64_t* block_off, const int32_t* n_blocks,
+                                         int32_t n_tracks, int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm,
+                                         int32_t d_chroma, const int32_t* pairs, int64_t n_pairs, double kappa,
+                                         int32_t K, float mu, int32_t binarize, double* scores_out, int32_t* seg_out,
+                                         void* hip_stream) {
+  return ef_batches(EF_LOCATE, "acoss_earlyfusion_locate", mfcc, ssm, chroma, chroma_med, block_off, n_blocks,
+                    n_tracks, max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, binarize, scores_out,
+                    seg_out, 0, nullptr, nullptr, hip_stream);
 }
 
 extern "C" int acoss_earlyfusion_locate(const float* mfcc, const float* ssm, const float* chroma,
@@ -721,9 +691,20 @@ extern "C" int acoss_earlyfusion_locate(const float* mfcc, const float* ssm, con
                                         int32_t n_tracks, int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm,
                                         int32_t d_chroma, const int32_t* pairs, int64_t n_pairs, double kappa,
                                         int32_t K, float mu, double* scores_out, int32_t* seg_out, void* hip_stream) {
-  return ef_batches(EF_LOCATE, "acoss_earlyfusion_locate", mfcc, ssm, chroma, chroma_med, block_off, n_blocks,
-                    n_tracks, max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, scores_out, seg_out,
-                    0, nullptr, nullptr, hip_stream);
+  return acoss_earlyfusion_locate2(mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, max_blocks, d_mfcc,
+                                   d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, ACOSS_EF_BIN_ROWS, scores_out,
+                                   seg_out, hip_stream);
+}
+
+extern "C" int acoss_earlyfusion_path2(const float* mfcc, const float* ssm, const float* chroma,
+                                       const float* chroma_med, const int64_t* block_off, const int32_t* n_blocks,
+                                       int32_t n_tracks, int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm,
+                                       int32_t d_chroma, const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K,
+                                       float mu, int32_t binarize, double* scores_out, int32_t* seg_out,
+                                       int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
+  return ef_batches(EF_PATH, "acoss_earlyfusion_path", mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks,
+                    max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, binarize, scores_out, seg_out,
+                    path_cap, len_out, path_out, hip_stream);
 }
 
 extern "C" int acoss_earlyfusion_path(const float* mfcc, const float* ssm, const float* chroma,
@@ -732,7 +713,7 @@ extern "C" int acoss_earlyfusion_path(const float* mfcc, const float* ssm, const
                                       int32_t d_chroma, const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K,
                                       float mu, double* scores_out, int32_t* seg_out, int32_t path_cap,
                                       int32_t* len_out, int32_t* path_out, void* hip_stream) {
-  return ef_batches(EF_PATH, "acoss_earlyfusion_path", mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks,
-                    max_blocks, d_mfcc, d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, scores_out, seg_out, path_cap,
-                    len_out, path_out, hip_stream);
+  return acoss_earlyfusion_path2(mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, max_blocks, d_mfcc,
+                                 d_ssm, d_chroma, pairs, n_pairs, kappa, K, mu, ACOSS_EF_BIN_ROWS, scores_out, seg_out,
+                                 path_cap, len_out, path_out, hip_stream);
 }

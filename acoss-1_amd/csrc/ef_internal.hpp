@@ -80,6 +80,32 @@ static_assert(kEfPack <= 64, "one pair per lane");
 int ef_launch_csms(const EfBank& B, const EfPrep& R, const int32_t* pairs, int P, int ld, int* oti, bool self_pairs,
                    float* C, int64_t mstride, hipStream_t st);
 
+// k1, k2 of getWCSMSSM and whether the reference can fuse the pair at all (early SNF)
+__device__ __forceinline__ bool snf_split(int M, int N, int K, int* k1, int* k2) {
+  *k1 = (int)((double)K * (double)M / (double)(M + N));
+  *k2 = K - *k1;
+  return *k1 >= 1 && *k1 <= M - 2 && *k2 >= 1 && *k2 <= N - 2 && K < M + N;
+}
+
+// csm_to_binary's row launch over `nplanes` CSM planes of P pairs (C + m * mstride + p * ld * ld)
+// into bit planes plane0 .. plane0 + nplanes - 1 of each pair's four (Wb, plane stride wplane):
+// k_ef_binarize_lanes, k_ef_binarize_small or k_ef_binarize by ld and kappa (earlyfusion.hip).
+int ef_launch_rowbin(const float* C, int64_t mstride, int ld, const EfPairs& E, int P, double kappa, uint16_t* Wb,
+                     int64_t wplane, int plane0, int nplanes, hipStream_t st);
+
+// The column half of the mutual rule (ef_mutual.hip; the definition: include/acoss_hip.h): clears,
+// in the bit planes the row launch wrote, the rows that are not among the count(kappa, M) smallest
+// of their column, ties to the lowest row. ppp: bit planes per pair (4; 1 for early SNF).
+int ef_launch_colpass(const float* C, int64_t mstride, int ld, const EfPairs& E, int P, double kappa, uint16_t* Wb,
+                      int64_t wplane, int plane0, int nplanes, hipStream_t st);
+// ... for early SNF: the LARGEST of each column of the float64 cross planes (cr + p * ld * ld), one
+// bit plane per pair; pairs that snf_split refuses keep their empty plane.
+int ef_launch_colpass_snf(const double* cr, int ld, const EfPairs& E, int P, int K, double kappa, uint16_t* Wb,
+                          int64_t wplane, hipStream_t st);
+// Bit plane 0 of each pair's ppp -> its M x N byte matrix, row-major at out + off[p].
+int ef_launch_unpack(const uint16_t* Wb, int64_t wplane, int ppp, int ld, const EfPairs& E, int P, const int64_t* off,
+                     uint8_t* out, hipStream_t st);
+
 // Smith-Waterman metadata of P pairs with `repeat` matrices each (matrix p * repeat + s of pair p):
 // rows = M, cols = N of the pair (earlyfusion.hip).
 int ef_launch_swmeta(const EfPairs& E, int P, int repeat, int32_t* rows, int32_t* cols, hipStream_t st);

@@ -20,7 +20,9 @@
 //                  k_efs_left (S B + reg_diag I), one launch each per step over (row, pair)
 //   k_efs_cross    F and the cross block (also to the caller's ragged cross_out)
 //   k_efs_binarize the nn largest of each row, ties to the lowest column, into the bit plane layout
-//                  of the Smith-Waterman kernels (u16 words of 16 rows)
+//                  of the Smith-Waterman kernels (u16 words of 16 rows); acoss_earlyfusion_snf2 with
+//                  ACOSS_EF_BIN_MUTUAL then runs the column pass of ef_mutual.hip over the plane, and
+//                  copies the plane out as bytes when binary_out is given
 // Both fusion regimes run the same float64 operations in the same order (each product sums over
 // the K neighbours in ascending column order from +0, one rounded multiply and one rounded add
 // per term), so a pair's bits do not depend on its regime, its chunk or its place in the list.
@@ -53,13 +55,6 @@ struct SnfPairs {
   EfPairs E;
   const int32_t *sa, *sb;  // per pair: its tracks' planes among the chunk's self distances
 };
-
-// k1, k2 of getWCSMSSM and whether the reference can fuse the pair at all
-__device__ __forceinline__ bool snf_split(int M, int N, int K, int* k1, int* k2) {
-  *k1 = (int)((double)K * (double)M / (double)(M + N));
-  *k2 = K - *k1;
-  return *k1 >= 1 && *k1 <= M - 2 && *k2 >= 1 && *k2 <= N - 2 && K < M + N;
-}
 
 // cross_off against the pairs' own M N, before any write: the first bad pair goes to bad[0]
 __global__ void k_efs_off_check(EfPairs E, int64_t n_pairs, const int64_t* __restrict__ cross_off, int64_t cross_total,
@@ -408,18 +403,26 @@ __global__ void k_efs_refused(EfPairs E, int P, int K, double* __restrict__ scor
 
 using namespace acoss;
 
-extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
-                                     const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
-                                     int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma,
-                                     const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K, float mu,
-                                     int32_t niters, double reg_diag, double* score_out, const int64_t* cross_off,
-                                     int64_t cross_total, double* cross_out, void* hip_stream) {
+namespace {
+
+// The one driver under acoss_earlyfusion_snf and acoss_earlyfusion_snf2.
+int efs_batches(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs, double kappa,
+                int32_t K, float mu, int32_t binarize, int32_t niters, double reg_diag, double* score_out,
+                const int64_t* cross_off, int64_t cross_total, double* cross_out, uint8_t* binary_out,
+                void* hip_stream) {
   clear_error();
+  if (binarize != ACOSS_EF_BIN_ROWS && binarize != ACOSS_EF_BIN_MUTUAL) {
+    set_error("acoss_earlyfusion_snf2: unknown binarize %d", binarize);
+    return ACOSS_E_ARG;
+  }
+  const bool ragged = cross_out || binary_out;  // either output is laid out by cross_off
   const EfBank B{mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, d_mfcc, d_ssm, d_chroma};
   // K against the lane limit only, whatever max_blocks is: the reference needs K < M + N, k1 <= M - 2
   // and k2 <= N - 2 of each pair (snf_split), and a pair that breaks them scores NaN on its own
   if (int rc = ef_check_args("acoss_earlyfusion_snf", B, max_blocks, pairs, n_pairs, kappa, K, kEfsKmax, score_out,
-                             niters < 0 || !(reg_diag >= 0.0) || (cross_out && (!cross_off || cross_total < 0))))
+                             niters < 0 || !(reg_diag >= 0.0) || (ragged && (!cross_off || cross_total < 0))))
     return rc;
   const int ld = (int)align_up((size_t)max_blocks, 4);
   if (2 * ld > kEfsNmax) {
@@ -434,7 +437,7 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
   unsigned long long* d_bad = static_cast<unsigned long long*>(workspace(27, 256));
   if (!d_bad) return ACOSS_E_HIP;
   unsigned long long h_bad = ~0ull;
-  if (cross_out) {
+  if (ragged) {
     ACOSS_HIP_CHECK(hipMemsetAsync(d_bad, 0xff, 8, s));
     hipLaunchKernelGGL(k_efs_off_check, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, Eall, n_pairs,
                        cross_off, cross_total, d_bad);
@@ -598,6 +601,10 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
     hipLaunchKernelGGL(k_efs_binarize, dim3((ld + 15) / 16, P), dim3(256), (size_t)ld * (4 * 8 + 4), s, cr, ld, E,
                        (int)K, kappa, Wb, wplane);
     ACOSS_LAUNCH_CHECK();
+    if (binarize == ACOSS_EF_BIN_MUTUAL)
+      if (int rc = ef_launch_colpass_snf(cr, ld, E, P, (int)K, kappa, Wb, wplane, s)) return rc;
+    if (binary_out)
+      if (int rc = ef_launch_unpack(Wb, wplane, 1, ld, E, P, cross_off + p0, binary_out, s)) return rc;
     prof_end(PH_BIN, s);
     prof_begin(PH_SW, s);
     if (int rc = ef_launch_swmeta(E, P, 1, m_rows, m_cols, s)) return rc;
@@ -607,4 +614,29 @@ extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const 
     prof_end(PH_SW, s);
   }
   return ACOSS_OK;
+}
+
+}  // namespace
+
+extern "C" int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                                     const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
+                                     int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma,
+                                     const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K, float mu,
+                                     int32_t niters, double reg_diag, double* score_out, const int64_t* cross_off,
+                                     int64_t cross_total, double* cross_out, void* hip_stream) {
+  return efs_batches(mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, max_blocks, d_mfcc, d_ssm, d_chroma,
+                     pairs, n_pairs, kappa, K, mu, ACOSS_EF_BIN_ROWS, niters, reg_diag, score_out, cross_off,
+                     cross_total, cross_out, nullptr, hip_stream);
+}
+
+extern "C" int acoss_earlyfusion_snf2(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                                      const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks,
+                                      int32_t max_blocks, int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma,
+                                      const int32_t* pairs, int64_t n_pairs, double kappa, int32_t K, float mu,
+                                      int32_t binarize, int32_t niters, double reg_diag, double* score_out,
+                                      const int64_t* cross_off, int64_t cross_total, double* cross_out,
+                                      uint8_t* binary_out, void* hip_stream) {
+  return efs_batches(mfcc, ssm, chroma, chroma_med, block_off, n_blocks, n_tracks, max_blocks, d_mfcc, d_ssm, d_chroma,
+                     pairs, n_pairs, kappa, K, mu, binarize, niters, reg_diag, score_out, cross_off, cross_total,
+                     cross_out, binary_out, hip_stream);
 }

@@ -656,6 +656,80 @@ int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const float* chro
                           double kappa, int32_t K, float mu, int32_t niters, double reg_diag, double* score_out,
                           const int64_t* cross_off, int64_t cross_total, double* cross_out, void* hip_stream);
 
+/* ---------------------------------------------------------------------------------
+ * EarlyFusion's binarisation by MUTUAL nearest neighbours (Tralie 2017, "Early MFCC and HPCP fusion
+ * for robust cover song identification"; the author's CSMToBinaryMutual = CSMToBinary(D) *
+ * CSMToBinary(D.T).T). The reference's csm_to_binary keeps the row half only (SURVEY.md appendix,
+ * defect 7), and that stays the default of every entry: ACOSS_EF_BIN_ROWS gives the twin's bits.
+ *
+ * "mutual": for a float32 M x N matrix D and kappa,
+ *   count(kappa, n) = int(np.round(kappa * n)) for kappa < 1 (float64 product, half to even: C rint;
+ *     at kappa = 0.1: 0 for n = 5, 2 for n = 15, 2 for n = 25), else int(kappa); the C ABI clamps a
+ *     count to its line length, min(count, n), as the row kernels always have. nn_r = count(kappa,
+ *     N), nn_c = count(kappa, M). kappa == 0 gives all ones.
+ *   Row rule:    R(i, j) = 1 iff fewer than nn_r cells of row i come before (i, j) in the order
+ *     (value ascending, column ascending): csm_to_binary with ties to the lowest column, what every
+ *     entry computes today.
+ *   Column rule: C(i, j) = 1 iff fewer than nn_c cells of column j come before (i, j) in the order
+ *     (value ascending, ROW ascending). The order on values is the row rule's (the float's bit
+ *     pattern mapped to an unsigned key, so -0 < +0), hence C(D) = R(D^T)^T bit for bit.
+ *   B = R & C.
+ * So B is a subset of R; row sums are at most nn_r and column sums at most nn_c; mutual(D^T) =
+ * mutual(D)^T exactly; for count-valued kappa the masks are nested in kappa. A short query against
+ * a long reference can have nn_c == 0 (M = 4, N = 30, kappa = 0.1: nn_r = 3, nn_c = 0): the mask is
+ * empty and the score 0, by definition.
+ * Early SNF: the matrix is the float64 cross block and both rules take the LARGEST values: R the
+ * nn_r largest of each row, ties to the lowest column (today's rule), C the nn_c largest of each
+ * column, ties to the lowest row (-0 == +0), B = R & C. A pair the reference cannot fuse keeps its
+ * NaN score and an empty matrix.
+ * The Python layer raises the reference's "kth(=%d) out of bounds (%d)" for nn_r >= N and, under
+ * mutual, for nn_c >= M; the C ABI clamps and does not raise. */
+#define ACOSS_EF_BIN_ROWS 0
+#define ACOSS_EF_BIN_MUTUAL 1
+
+/* acoss_earlyfusion, acoss_earlyfusion_locate and acoss_earlyfusion_path with `binarize` (one of
+ * the two values above; anything else: ACOSS_E_ARG) directly after mu; everything else as the
+ * twin, which forwards here with ACOSS_EF_BIN_ROWS. Under ACOSS_EF_BIN_MUTUAL the column pass
+ * (csrc/ef_mutual.hip) runs after each row-binarise launch, over the three CSM planes before the
+ * fusion overwrites the first, and over the early matrix; with ACOSS_EF_BIN_ROWS nothing new runs. */
+int acoss_earlyfusion2(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                       const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                       int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
+                       double kappa, int32_t K, float mu, int32_t binarize, double* scores_out, void* hip_stream);
+int acoss_earlyfusion_locate2(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                              const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                              int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
+                              double kappa, int32_t K, float mu, int32_t binarize, double* scores_out,
+                              int32_t* seg_out, void* hip_stream);
+int acoss_earlyfusion_path2(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                            const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                            int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
+                            double kappa, int32_t K, float mu, int32_t binarize, double* scores_out, int32_t* seg_out,
+                            int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream);
+
+/* acoss_earlyfusion_snf with `binarize` after mu and `binary_out` before the stream. binary_out:
+ * NULL, or pair p's M x N binary matrix (uint8) as the Smith-Waterman kernel reads it, row-major at
+ * binary_out[cross_off[p] ..); all zero for a pair that cannot be fused. cross_off is then required
+ * (and checked against cross_total) even when cross_out is NULL. */
+int acoss_earlyfusion_snf2(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
+                           const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,
+                           int32_t d_mfcc, int32_t d_ssm, int32_t d_chroma, const int32_t* pairs, int64_t n_pairs,
+                           double kappa, int32_t K, float mu, int32_t binarize, int32_t niters, double reg_diag,
+                           double* score_out, const int64_t* cross_off, int64_t cross_total, double* cross_out,
+                           uint8_t* binary_out, void* hip_stream);
+
+/* The binarisation alone, for a batch of float32 matrices in acoss_sw_constrained's layout (matrix
+ * b: rows[b] x cols[b], row-major at mats + off[b]; every array a device pointer): out (uint8, the
+ * same offsets) = the row rule (ACOSS_EF_BIN_ROWS) or the mutual rule of each matrix. It runs the
+ * pipeline's own kernels: the row launch acoss_earlyfusion would choose for ld = align_up(max(
+ * max_rows, max_cols), 4) (so max_rows and max_cols pick the shape class), then the column pass,
+ * on planes padded to ld x ld; a made-up bank (n_blocks = {rows0, cols0, rows1, cols1, ...}, pairs
+ * (2 b, 2 b + 1)) stands for the tracks. ACOSS_E_ARG for kappa < 0, an unknown binarize, ld above
+ * 16384, or a matrix with no rows or columns or more than max_rows x max_cols. */
+int acoss_binarize_mutual(const float* mats, const int64_t* off, const int32_t* rows, const int32_t* cols,
+                          int32_t n_mats, int32_t max_rows, int32_t max_cols, double kappa, int32_t binarize,
+                          uint8_t* out, void* hip_stream);
+
 /* EarlyFusion beat-synchronous block features of a batch of tracks (replaces
  * EarlyFusion.load_features' block loops, acoss/algorithms/earlyfusion_traile.py:67-154, and its
  * skimage resize_block, :214-247, restated in float64). Track t: chroma frames [frame_off[t],
