@@ -14,12 +14,9 @@
 //   ef_prepare, ef_launch_csms   the per-track preparation, once per call, and the three CSMs of a
 //                 chunk (ef_csm.hip, through ef_internal.hpp)
 //   binarize      csm_to_binary: the round(kappa * N) smallest of each row -> 1, ties lowest
-//                 column, into u16 bit words of 16 rows (the SW input). Tracks of at most 64 blocks
-//                 and nn <= 8: k_ef_binarize_lanes, a wave per (pair, matrix) with a row per lane;
-//                 at most 64 blocks otherwise: k_ef_binarize_small, a block per (pair, matrix);
-//                 longer tracks: k_ef_binarize, a wave per row (knockout rounds or a radix select);
-//                 ef_launch_rowbin picks among them. Under ACOSS_EF_BIN_MUTUAL (the entries ending
-//                 in 2) the column pass of ef_mutual.hip then clears what the columns do not keep
+//                 column, into u16 bit words of 16 rows (the SW input): ef_launch_rowbin. Under
+//                 ACOSS_EF_BIN_MUTUAL (the entries ending in 2) ef_launch_colpass then clears what
+//                 the columns do not keep. The kernels and their shape classes: ef_binarize.hip
 //   k_ef_kmin*    mean of the K smallest of each row (k_ef_kmin_rows, a wave per 64 rows through
 //                 LDS tiles) and column (k_ef_kmin, a thread per column), K <= 16; k_ef_kmean, a
 //                 wave-per-line select, beyond that
@@ -36,249 +33,13 @@
 
 #include "common.hpp"
 #include "ef_internal.hpp"
-#include "ef_select.hpp"
 #include "sw_internal.hpp"
 
 namespace acoss {
 
 namespace {
 
-constexpr int kBinRegs = 16;  // row keys per lane kept in registers by k_ef_binarize (N <= 1024)
-constexpr int kKmax = 16;     // largest K of the streaming k-smallest means
-
-__device__ __forceinline__ unsigned fkey(float f) {
-  const unsigned u = __builtin_bit_cast(unsigned, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// The nn smallest of every row -> 1, ties lowest column (csm_to_binary). A block of 16 waves
-// takes 16 rows (one wave per row) and writes them as one row of u16 bit words (bit r = row
-// 16g + r) in LDS, then to the pair's bit plane for SW. blockIdx.z = CSM plane, written to
-// bit plane z + plane0 of the pair (plane stride = wplane words, 4 planes per pair).
-template <int KB>  // keys per lane held in registers (rows of up to 64 * KB columns)
-__device__ __forceinline__ void ef_binarize_row(const float* __restrict__ x, int N, double kappa, int lane,
-                                                unsigned* bits, unsigned bit, unsigned* hist) {
-  if (kappa == 0.0) {
-    for (int c = lane; c < N; c += 64) atomicOr(&bits[c], bit);
-    return;
-  }
-  // np.round: half to even. The host wrapper rejects nn >= N as the reference's argpartition does;
-  // the clamp keeps the radix select's rank inside the row if the ABI is called directly
-  const int nn = min(kappa < 1.0 ? (int)rint(kappa * (double)N) : (int)kappa, N);
-  if (nn <= 0) return;
-  const int per = (N + 63) / 64;
-  const int c0 = lane * per, c1 = min(N, c0 + per);
-  unsigned lo = 0, hi = 0xffffffffu;
-  unsigned kr[KB];
-  const bool inreg = per <= KB;
-  if (inreg) {  // the row's keys in registers: one pass over memory
-#pragma unroll
-    for (int q = 0; q < KB; ++q) kr[q] = (q < per && c0 + q < c1) ? fkey(x[c0 + q]) : 0xffffffffu;
-    unsigned mn = 0xffffffffu, mx = 0u;  // bound the search by the row's range
-#pragma unroll
-    for (int q = 0; q < KB; ++q) {
-      mn = min(mn, kr[q]);
-      if (q < per && c0 + q < c1) mx = max(mx, kr[q]);
-    }
-    lo = wave_min_u32(mn);
-    hi = wave_max_u32(mx);
-    lo = radix_kth(kr, lo, hi, nn, lane, hist);
-  } else {
-    while (lo < hi) {
-      const unsigned mid = lo + ((hi - lo) >> 1);
-      int c = 0;
-      for (int k = c0; k < c1; ++k) c += fkey(x[k]) <= mid;
-      if (wave_sum(c) >= nn)
-        hi = mid;
-      else
-        lo = mid + 1;
-    }
-  }
-  const unsigned kth = lo;
-  int less = 0, eq = 0;
-  if (inreg) {  // the keys are still in registers: no second and third read of the row
-#pragma unroll
-    for (int q = 0; q < KB; ++q) {
-      less += kr[q] < kth;
-      eq += kr[q] == kth;
-    }
-    const int take_eq = nn - wave_sum(less);
-    int seen = wave_incl_scan(eq) - eq;
-#pragma unroll
-    for (int q = 0; q < KB; ++q) {
-      bool v = kr[q] < kth;
-      if (kr[q] == kth && q < per && c0 + q < c1) {
-        v = seen < take_eq;
-        ++seen;
-      }
-      if (v) atomicOr(&bits[c0 + q], bit);
-    }
-    return;
-  }
-  for (int k = c0; k < c1; ++k) {
-    const unsigned kk = fkey(x[k]);
-    less += kk < kth;
-    eq += kk == kth;
-  }
-  const int take_eq = nn - wave_sum(less);
-  int seen = wave_incl_scan(eq) - eq;
-  for (int k = c0; k < c1; ++k) {
-    const unsigned kk = fkey(x[k]);
-    bool v = kk < kth;
-    if (kk == kth) {
-      v = seen < take_eq;
-      ++seen;
-    }
-    if (v) atomicOr(&bits[k], bit);
-  }
-}
-
-// Rows of at most 64 columns (one key per lane) with a small nn (Da-TACOS beat blocks: N ~ 14..47,
-// nn = round(kappa N) ~ 1..5): nn rounds of (wave minimum of the remaining keys, the lowest lane
-// holding it leaves and sets its bit). Each round takes the least remaining key and, among equal
-// keys, the lowest column, so the nn lanes taken are exactly csm_to_binary's nn smallest with ties
-// to the lowest column -- the radix select's answer at a fraction of its passes.
-__device__ __forceinline__ void ef_binarize_row_knock(const float* __restrict__ x, int N, int nn, int lane,
-                                                      unsigned* bits, unsigned bit) {
-  unsigned k = lane < N ? fkey(x[lane]) : 0xffffffffu;
-  bool alive = lane < N;
-  for (int t = 0; t < nn; ++t) {  // wave-uniform
-    const unsigned m = wave_min_u32(alive ? k : 0xffffffffu);
-    const int src = __builtin_ctzll(__ballot(alive && k == m));
-    if (lane == src) {
-      alive = false;
-      atomicOr(&bits[lane], bit);
-    }
-  }
-}
-constexpr int kKnockMax = 16;  // largest nn taken by ef_binarize_row_knock
-
-__global__ __launch_bounds__(1024) void k_ef_binarize(const float* __restrict__ C, int64_t mat_stride, int ld,
-                                                      EfPairs E, double kappa, uint16_t* __restrict__ Wb,
-                                                      int64_t wplane, int plane0) {
-  extern __shared__ unsigned bits[];
-  __shared__ __attribute__((aligned(16))) unsigned s_hist[16][256 + 64];  // radix_kth, one per wave
-  const int p = blockIdx.y, m = blockIdx.z, g = blockIdx.x;
-  int a, b, M, N;
-  pair_dims(E, p, &a, &b, &M, &N);
-  if (16 * g >= M) return;  // whole block: no barrier skipped by part of it
-  for (int c = threadIdx.x; c < N; c += 1024) bits[c] = 0;
-  __syncthreads();
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int row = 16 * g + w;
-  if (row < M) {
-    const float* xr = C + m * mat_stride + (size_t)p * ld * ld + (size_t)row * ld;
-    const int nn = min(kappa < 1.0 ? (int)rint(kappa * (double)N) : (int)kappa, N);  // as ef_binarize_row
-    if (N <= 64 && kappa != 0.0 && nn <= kKnockMax) {
-      if (nn > 0) ef_binarize_row_knock(xr, N, nn, lane, bits, 1u << w);
-    } else if (N <= 64 * 8)  // EarlyFusion's ~450-block tracks: 8 key registers halve the count passes
-      ef_binarize_row<8>(xr, N, kappa, lane, bits, 1u << w, s_hist[w]);
-    else
-      ef_binarize_row<kBinRegs>(xr, N, kappa, lane, bits, 1u << w, s_hist[w]);
-  }
-  __syncthreads();
-  uint16_t* o = Wb + ((size_t)p * 4 + plane0 + m) * wplane + (size_t)g * ld;
-  for (int c = threadIdx.x; c < N; c += 1024) o[c] = (uint16_t)bits[c];
-}
-
-// k_ef_binarize for batches whose tracks all have at most 64 blocks and a small nn (Da-TACOS beat
-// blocks, kappa = 0.1: nn = 1..6): ONE WAVE per (pair, matrix), lane r = row r. The lane loads its
-// row's keys into registers (16-byte loads), then nn rounds each take the row's least key not yet
-// taken (strict <, columns ascending: the lowest column among equal keys, as csm_to_binary's tie
-// rule here); a ballot per column then gives lane c its column's 64-bit row mask, which
-// it writes as the u16 words of the SW bit plane. No LDS, no barrier, no cross-lane reduction per
-// round (k_ef_binarize_small spent 4 waves, two block barriers and a 6-stage wave minimum per round
-// and row). Same selected set as every other binarize kernel.
-__global__ __launch_bounds__(256) void k_ef_binarize_lanes(const float* __restrict__ C, int64_t mat_stride, int ld,
-                                                           EfPairs E, double kappa, uint16_t* __restrict__ Wb,
-                                                           int64_t wplane, int plane0, int nplanes, int n_units) {
-  const int unit = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (unit >= n_units) return;
-  const int p = unit / nplanes, m = unit - p * nplanes;
-  int a, b, M, N;
-  pair_dims(E, p, &a, &b, &M, &N);
-  const int lane = threadIdx.x & 63;
-  const int nn = min(kappa < 1.0 ? (int)rint(kappa * (double)N) : (int)kappa, N);  // as ef_binarize_row
-  unsigned long long sel = 0ull;  // this lane's row: its selected columns
-  if (kappa == 0.0) {
-    sel = N >= 64 ? ~0ull : ((1ull << N) - 1ull);
-  } else if (nn > 0) {
-    const float* xr = C + m * mat_stride + (size_t)p * ld * ld + (size_t)min(lane, M - 1) * ld;
-    unsigned key[64];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      if (4 * q < N) {  // wave-uniform; ld is a multiple of 4, so the 16-byte load stays in the row
-        const f32x4e v = *reinterpret_cast<const f32x4e*>(xr + 4 * q);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) key[4 * q + u] = 4 * q + u < N ? fkey(v[u]) : 0xffffffffu;
-      } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) key[4 * q + u] = 0xffffffffu;
-      }
-    }
-#pragma unroll 1
-    for (int t = 0; t < nn; ++t) {  // wave-uniform; nn <= N, so an untaken column always exists
-      unsigned bk = 0xffffffffu;
-      int bc = -1;
-#pragma unroll
-      for (int c = 0; c < 64; ++c) {
-        if (c < N) {  // wave-uniform
-          const bool better = !((sel >> c) & 1ull) && (bc < 0 || key[c] < bk);
-          bk = better ? key[c] : bk;
-          bc = better ? c : bc;
-        }
-      }
-      sel |= 1ull << bc;
-    }
-  }
-  const unsigned long long rows = M >= 64 ? ~0ull : ((1ull << M) - 1ull);
-  unsigned long long colbits = 0ull;
-#pragma unroll
-  for (int c = 0; c < 64; ++c) {
-    if (c < N) {
-      const unsigned long long bcol = __ballot((sel >> c) & 1ull) & rows;
-      colbits = lane == c ? bcol : colbits;
-    }
-  }
-  const int ng = (M + 15) / 16;
-  uint16_t* o = Wb + ((size_t)p * 4 + plane0 + m) * wplane;
-  if (lane < N)
-    for (int g = 0; g < ng; ++g) o[(size_t)g * ld + lane] = (uint16_t)(colbits >> (16 * g));
-}
-
-// k_ef_binarize for batches whose tracks all have at most 64 blocks (Da-TACOS beat blocks): ONE
-// 256-thread block per (pair, matrix) instead of a 1024-thread block per 16 rows; wave w takes
-// rows w, w + 4, ... with the same per-row selects as k_ef_binarize, into LDS words of 16 rows.
-__global__ __launch_bounds__(256) void k_ef_binarize_small(const float* __restrict__ C, int64_t mat_stride, int ld,
-                                                           EfPairs E, double kappa, uint16_t* __restrict__ Wb,
-                                                           int64_t wplane, int plane0) {
-  __shared__ unsigned bits[4][64];
-  __shared__ __attribute__((aligned(16))) unsigned s_hist[4][256 + 64];  // radix_kth, one per wave
-  const int p = blockIdx.x, m = blockIdx.y;
-  int a, b, M, N;
-  pair_dims(E, p, &a, &b, &M, &N);
-  for (int e = threadIdx.x; e < 4 * 64; e += 256) bits[e >> 6][e & 63] = 0u;
-  __syncthreads();
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nn = min(kappa < 1.0 ? (int)rint(kappa * (double)N) : (int)kappa, N);  // as ef_binarize_row
-  for (int row = w; row < M; row += 4) {
-    const float* xr = C + m * mat_stride + (size_t)p * ld * ld + (size_t)row * ld;
-    unsigned* brow = bits[row >> 4];
-    const unsigned bit = 1u << (row & 15);
-    if (kappa != 0.0 && nn <= kKnockMax) {
-      if (nn > 0) ef_binarize_row_knock(xr, N, nn, lane, brow, bit);
-    } else {
-      ef_binarize_row<8>(xr, N, kappa, lane, brow, bit, s_hist[w]);
-    }
-  }
-  __syncthreads();
-  const int ng = (M + 15) / 16;
-  uint16_t* o = Wb + ((size_t)p * 4 + plane0 + m) * wplane;
-  for (int e = threadIdx.x; e < ng * 64; e += 256) {
-    const int g = e >> 6, c = e & 63;
-    if (c < N) o[(size_t)g * ld + c] = (uint16_t)bits[g][c];
-  }
-}
+constexpr int kKmax = 16;  // largest K of the streaming k-smallest means
 
 // Mean of the k smallest of each row (COLS = false) or column (K > kKmax); blockIdx.z = matrix;
 // canonical order (kmean_canon, common.hpp), as k_ef_kmin.
@@ -442,29 +203,6 @@ __global__ void k_ef_swmeta(EfPairs E, int P, int repeat, int32_t* rows, int32_t
 
 int ef_launch_swmeta(const EfPairs& E, int P, int repeat, int32_t* rows, int32_t* cols, hipStream_t st) {
   hipLaunchKernelGGL(k_ef_swmeta, dim3((P + 255) / 256), dim3(256), 0, st, E, P, repeat, rows, cols);
-  ACOSS_LAUNCH_CHECK();
-  return ACOSS_OK;
-}
-
-int ef_launch_rowbin(const float* C, int64_t mstride, int ld, const EfPairs& E, int P, double kappa, uint16_t* Wb,
-                     int64_t wplane, int plane0, int nplanes, hipStream_t st) {
-  // one binarize block per (pair, matrix) when every track has at most 64 blocks (15,000 Da-TACOS-
-  // shape songs: 4.04M -> 4.38M pairs/s, profiles/r05/ef_short/efbin15k_*.log)
-  const bool small_bin = ld <= 64;
-  // ... and one wave per (pair, matrix) with a row per lane when every row's nn is small (the nn
-  // rounds cost nn passes over the row's registers); ACOSS_EF_LANEBIN=0 keeps k_ef_binarize_small
-  const int nn_max = kappa < 1.0 ? (int)rint(kappa * 64.0) : (int)kappa;
-  static const bool lanebin_env = !(getenv("ACOSS_EF_LANEBIN") && getenv("ACOSS_EF_LANEBIN")[0] == '0');
-  const bool lane_bin = small_bin && lanebin_env && nn_max <= 8;
-  if (lane_bin)
-    hipLaunchKernelGGL(k_ef_binarize_lanes, dim3((unsigned)((nplanes * P + 3) / 4)), dim3(256), 0, st, C, mstride, ld,
-                       E, kappa, Wb, wplane, plane0, nplanes, nplanes * P);
-  else if (small_bin)
-    hipLaunchKernelGGL(k_ef_binarize_small, dim3(P, nplanes), dim3(256), 0, st, C, mstride, ld, E, kappa, Wb, wplane,
-                       plane0);
-  else  // k_ef_binarize keeps one u32 per column in LDS
-    hipLaunchKernelGGL(k_ef_binarize, dim3((ld + 15) / 16, P, nplanes), dim3(1024), (size_t)ld * 4, st, C, mstride, ld,
-                       E, kappa, Wb, wplane, plane0);
   ACOSS_LAUNCH_CHECK();
   return ACOSS_OK;
 }

@@ -1,6 +1,7 @@
 // ef_internal.hpp — what earlyfusion.hip (the four scores) and ef_snf.hip (the per-pair similarity
 // network fusion) share: the per-track preparation and the three CSMs of EarlyFusion (ef_csm.hip),
-// the entries' common argument check and chunk budget, and the Smith-Waterman metadata launch.
+// the entries' common argument check and chunk budget, the binarisation launchers (ef_binarize.hip)
+// and the Smith-Waterman metadata launch.
 #pragma once
 #include <cstdlib>
 
@@ -87,22 +88,23 @@ __device__ __forceinline__ bool snf_split(int M, int N, int K, int* k1, int* k2)
   return *k1 >= 1 && *k1 <= M - 2 && *k2 >= 1 && *k2 <= N - 2 && K < M + N;
 }
 
-// csm_to_binary's row launch over `nplanes` CSM planes of P pairs (C + m * mstride + p * ld * ld)
-// into bit planes plane0 .. plane0 + nplanes - 1 of each pair's four (Wb, plane stride wplane):
-// k_ef_binarize_lanes, k_ef_binarize_small or k_ef_binarize by ld and kappa (earlyfusion.hip).
+// The binarisation launchers (ef_binarize.hip: the rule and the kernel of every shape class). Bit
+// planes: Wb, plane stride wplane, ppp per pair (4; 1 for early SNF). rowbin: csm_to_binary over
+// `nplanes` CSM planes of P pairs (C + m * mstride + p * ld * ld) into bit planes plane0 .. plane0 +
+// nplanes - 1 of each pair's four. colpass: the column half of the mutual rule (the definition:
+// include/acoss_hip.h) clears, in those planes, the rows that are not among the count(kappa, M)
+// smallest of their column, ties to the lowest row. _snf: the LARGEST of each row / column of early
+// SNF's float64 cross planes (cr + p * ld * ld), one bit plane per pair; a pair that snf_split
+// refuses gets / keeps an empty plane. unpack: bit plane 0 of each pair's ppp -> its M x N byte
+// matrix, row-major at out + off[p].
 int ef_launch_rowbin(const float* C, int64_t mstride, int ld, const EfPairs& E, int P, double kappa, uint16_t* Wb,
                      int64_t wplane, int plane0, int nplanes, hipStream_t st);
-
-// The column half of the mutual rule (ef_mutual.hip; the definition: include/acoss_hip.h): clears,
-// in the bit planes the row launch wrote, the rows that are not among the count(kappa, M) smallest
-// of their column, ties to the lowest row. ppp: bit planes per pair (4; 1 for early SNF).
 int ef_launch_colpass(const float* C, int64_t mstride, int ld, const EfPairs& E, int P, double kappa, uint16_t* Wb,
                       int64_t wplane, int plane0, int nplanes, hipStream_t st);
-// ... for early SNF: the LARGEST of each column of the float64 cross planes (cr + p * ld * ld), one
-// bit plane per pair; pairs that snf_split refuses keep their empty plane.
+int ef_launch_rowbin_snf(const double* cr, int ld, const EfPairs& E, int P, int K, double kappa, uint16_t* Wb,
+                         int64_t wplane, hipStream_t st);
 int ef_launch_colpass_snf(const double* cr, int ld, const EfPairs& E, int P, int K, double kappa, uint16_t* Wb,
                           int64_t wplane, hipStream_t st);
-// Bit plane 0 of each pair's ppp -> its M x N byte matrix, row-major at out + off[p].
 int ef_launch_unpack(const uint16_t* Wb, int64_t wplane, int ppp, int ld, const EfPairs& E, int P, const int64_t* off,
                      uint8_t* out, hipStream_t st);
 

@@ -1,9 +1,61 @@
-// ef_select.hpp — the wave-per-line radix select that the row binarisation (earlyfusion.hip) and
-// the column pass of the mutual rule (ef_mutual.hip) share.
+// ef_select.hpp — csm_to_binary's line select, once: the count(kappa, n) least cells of a line
+// become 1, ties to the lowest index. The count, the keys and the three selects (knock64,
+// wave_line_select, wave_line_select_stream) under every kernel of ef_binarize.hip, rows and columns,
+// and k_binarize_rows (misc.hip). A kernel brings its own loads (keys into registers, or a key
+// reader) and its own emit (bits into words). The selects take nn >= 1; kappa == 0 (all ones),
+// nn <= 0 and a line that keeps everything stay with the callers.
 #pragma once
 #include "common.hpp"
 
 namespace acoss {
+
+// The count for a line of n: np.round (half to even) of kappa n, or kappa itself from 1 on. The host
+// wrappers reject a count >= n as the reference's argpartition does; the clamp is for direct callers.
+__host__ __device__ __forceinline__ int ef_count(double kappa, int n) {
+  return min(kappa < 1.0 ? (int)rint(kappa * (double)n) : (int)kappa, n);
+}
+
+// Keys whose unsigned order is a select's order on values: float32 ascending (fkey_f32, common.hpp:
+// -0 before +0), float64 descending for early SNF's largest (-0 counted as +0, as its row kernel).
+template <typename T>
+struct ColKey;
+template <>
+struct ColKey<float> {
+  typedef unsigned K;
+  static constexpr int kBits = 32;
+  static __device__ __forceinline__ K key(float f) { return fkey_f32(f); }
+};
+template <>
+struct ColKey<double> {
+  typedef unsigned long long K;
+  static constexpr int kBits = 64;
+  static __device__ __forceinline__ K key(double d) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, d + 0.0);
+    return (u >> 63) ? u : ~(u | 0x8000000000000000ull);
+  }
+};
+
+// Lane-private: the nn least of key[0..n) in (key ascending, index ascending) as a 64-bit mask, by
+// nn knock-out rounds (each takes the least key not yet taken, strict <, indices ascending: the
+// lowest index among equal keys). n, nn wave-uniform, 1 <= nn <= n <= 64. No LDS, no cross-lane step.
+__device__ __forceinline__ unsigned long long knock64(const unsigned (&key)[64], int n, int nn) {
+  unsigned long long sel = 0ull;
+#pragma unroll 1
+  for (int t = 0; t < nn; ++t) {  // wave-uniform; nn <= n, so an untaken index always exists
+    unsigned bk = 0xffffffffu;
+    int bi = -1;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+      if (i < n) {  // wave-uniform
+        const bool better = !((sel >> i) & 1ull) && (bi < 0 || key[i] < bk);
+        bk = better ? key[i] : bk;
+        bi = better ? i : bi;
+      }
+    }
+    sel |= 1ull << bi;
+  }
+  return sel;
+}
 
 // The nn-th smallest (1-based) of the wave's keys kr (KB per lane) within [lo, hi], by radix
 // select: from the highest bit where lo and hi differ, 8-bit digits, each digit from one LDS
@@ -63,6 +115,93 @@ __device__ __forceinline__ unsigned radix_kth(const unsigned (&kr)[KB], unsigned
     __builtin_amdgcn_wave_barrier();
   }
   return prefix;
+}
+
+// Wave per line, the line's keys in registers: lane l holds kr[q] = key of index i0 + q for
+// q < per, i0 + q < i1 (i0 = l per, i1 = min(n, i0 + per)) and 0xffffffff padding beyond (a NaN can
+// have that key too, hence the guards). wave_line_kth: the nn-th key, by radix_kth within the wave's
+// range of real keys. wave_line_keep: emit(q, keep) for q = 0 .. KB - 1, keep = the key is below
+// kth, or equals it and fewer than nn - #below equal keys come before in index order.
+// wave_line_select: both.
+template <int KB>
+__device__ __forceinline__ unsigned wave_line_kth(const unsigned (&kr)[KB], int per, int i0, int i1, int nn, int lane,
+                                                  unsigned* hist) {
+  unsigned mn = 0xffffffffu, mx = 0u;  // bound the search by the line's range
+#pragma unroll
+  for (int q = 0; q < KB; ++q) {
+    mn = min(mn, kr[q]);
+    if (q < per && i0 + q < i1) mx = max(mx, kr[q]);
+  }
+  return radix_kth(kr, wave_min_u32(mn), wave_max_u32(mx), nn, lane, hist);
+}
+template <int KB, class Emit>
+__device__ __forceinline__ void wave_line_keep(const unsigned (&kr)[KB], unsigned kth, int per, int i0, int i1, int nn,
+                                               Emit emit) {
+  int less = 0, eq = 0;
+#pragma unroll
+  for (int q = 0; q < KB; ++q) {
+    less += kr[q] < kth;
+    eq += kr[q] == kth;
+  }
+  const int take_eq = nn - wave_sum(less);
+  int seen = wave_incl_scan(eq) - eq;
+#pragma unroll
+  for (int q = 0; q < KB; ++q) {
+    bool v = kr[q] < kth;
+    if (kr[q] == kth && q < per && i0 + q < i1) {
+      v = seen < take_eq;
+      ++seen;
+    }
+    emit(q, v);
+  }
+}
+template <int KB, class Emit>
+__device__ __forceinline__ void wave_line_select(const unsigned (&kr)[KB], int per, int i0, int i1, int nn, int lane,
+                                                 unsigned* hist, Emit emit) {
+  wave_line_keep(kr, wave_line_kth(kr, per, i0, i1, nn, lane, hist), per, i0, i1, nn, emit);
+}
+
+// Wave per line of any length, nothing kept: lane l reads the keys at(k) of its indices [i0, i1)
+// again in every pass. wave_stream_kth: the least key with #(keys <= kth) >= nn by bisection over
+// [0, 0xffffffff]. wave_stream_keep: one pass for the less / equal counts, one that calls
+// emit(k, keep) for every k. wave_line_select_stream: both.
+template <class At>
+__device__ __forceinline__ unsigned wave_stream_kth(At at, int i0, int i1, int nn) {
+  unsigned lo = 0, hi = 0xffffffffu;
+  while (lo < hi) {
+    const unsigned mid = lo + ((hi - lo) >> 1);
+    int c = 0;
+    for (int k = i0; k < i1; ++k) c += at(k) <= mid;
+    if (wave_sum(c) >= nn)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  return lo;
+}
+template <class At, class Emit>
+__device__ __forceinline__ void wave_stream_keep(At at, unsigned kth, int i0, int i1, int nn, Emit emit) {
+  int less = 0, eq = 0;
+  for (int k = i0; k < i1; ++k) {
+    const unsigned kk = at(k);
+    less += kk < kth;
+    eq += kk == kth;
+  }
+  const int take_eq = nn - wave_sum(less);  // equal keys taken in index order
+  int seen = wave_incl_scan(eq) - eq;
+  for (int k = i0; k < i1; ++k) {
+    const unsigned kk = at(k);
+    bool v = kk < kth;
+    if (kk == kth) {
+      v = seen < take_eq;
+      ++seen;
+    }
+    emit(k, v);
+  }
+}
+template <class At, class Emit>
+__device__ __forceinline__ void wave_line_select_stream(At at, int i0, int i1, int nn, Emit emit) {
+  wave_stream_keep(at, wave_stream_kth(at, i0, i1, nn), i0, i1, nn, emit);
 }
 
 }  // namespace acoss

@@ -19,10 +19,11 @@
 //                  longer pairs: k_efs_diffuse (B = A S^T, a row of A in LDS per block) and
 //                  k_efs_left (S B + reg_diag I), one launch each per step over (row, pair)
 //   k_efs_cross    F and the cross block (also to the caller's ragged cross_out)
-//   k_efs_binarize the nn largest of each row, ties to the lowest column, into the bit plane layout
-//                  of the Smith-Waterman kernels (u16 words of 16 rows); acoss_earlyfusion_snf2 with
-//                  ACOSS_EF_BIN_MUTUAL then runs the column pass of ef_mutual.hip over the plane, and
-//                  copies the plane out as bytes when binary_out is given
+//   binarize       ef_launch_rowbin_snf (k_efs_binarize, ef_binarize.hip): the nn largest of each row,
+//                  ties to the lowest column, into the bit plane layout of the Smith-Waterman kernels
+//                  (u16 words of 16 rows); acoss_earlyfusion_snf2 with ACOSS_EF_BIN_MUTUAL then runs
+//                  ef_launch_colpass_snf over the plane, and copies the plane out as bytes when
+//                  binary_out is given
 // Both fusion regimes run the same float64 operations in the same order (each product sums over
 // the K neighbours in ascending column order from +0, one rounded multiply and one rounded add
 // per term), so a pair's bits do not depend on its regime, its chunk or its place in the list.
@@ -344,52 +345,6 @@ __global__ void k_efs_cross(const double* __restrict__ X, int ld, EfPairs E, int
   if (cross_out) cross_out[cross_off[p] + (int64_t)i * N + j] = v;
 }
 
-// The nn LARGEST of every row of cross -> 1, ties to the lowest column (csm_to_binary of
-// exp(-cross)): column c is taken when fewer than nn columns come before it in that order. A block
-// takes 16 rows (4 waves, 4 rows each, a row at a time in the wave's LDS line) and writes them as
-// one row of u16 words of the pair's bit plane. A pair the reference cannot fuse gets an empty plane.
-__global__ __launch_bounds__(256) void k_efs_binarize(const double* __restrict__ cr, int ld, EfPairs E, int K,
-                                                      double kappa, uint16_t* __restrict__ Wb, int64_t wplane) {
-  extern __shared__ double s_line[];  // 4 lines of ld doubles, then ld u32 bit words
-  const int p = blockIdx.y, g = blockIdx.x;
-  int a, b, M, N, k1, k2;
-  pair_dims(E, p, &a, &b, &M, &N);
-  if (16 * g >= M) return;  // the whole block
-  unsigned* bits = reinterpret_cast<unsigned*>(s_line + 4 * ld);
-  for (int c = threadIdx.x; c < N; c += 256) bits[c] = 0u;
-  __syncthreads();
-  const bool ok = snf_split(M, N, K, &k1, &k2);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nn = min(kappa < 1.0 ? (int)rint(kappa * (double)N) : (int)kappa, N);  // as ef_binarize_row
-  double* line = s_line + w * ld;
-  for (int q = 0; q < 4 && ok; ++q) {
-    const int rr = w + 4 * q, row = 16 * g + rr;
-    if (row >= M) break;  // wave-uniform
-    const double* x = cr + (size_t)p * ld * ld + (size_t)row * ld;
-    __builtin_amdgcn_wave_barrier();
-    for (int c = lane; c < N; c += 64) line[c] = x[c];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int c = lane; c < N; c += 64) {
-      bool take = kappa == 0.0;
-      if (!take) {
-        const double v = line[c];
-        int before = 0;
-        for (int j = 0; j < N; ++j) {
-          const double u = line[j];
-          before += (u > v || (u == v && j < c)) ? 1 : 0;
-        }
-        take = before < nn;
-      }
-      if (take) atomicOr(&bits[c], 1u << rr);
-    }
-  }
-  __syncthreads();
-  uint16_t* o = Wb + (size_t)p * wplane + (size_t)g * ld;
-  for (int c = threadIdx.x; c < N; c += 256) o[c] = (uint16_t)bits[c];
-}
-
 __global__ void k_efs_refused(EfPairs E, int P, int K, double* __restrict__ score) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
@@ -598,9 +553,7 @@ int efs_batches(const float* mfcc, const float* ssm, const float* chroma, const 
     ACOSS_LAUNCH_CHECK();
     prof_end(PH_SNF, s);
     prof_begin(PH_BIN, s);
-    hipLaunchKernelGGL(k_efs_binarize, dim3((ld + 15) / 16, P), dim3(256), (size_t)ld * (4 * 8 + 4), s, cr, ld, E,
-                       (int)K, kappa, Wb, wplane);
-    ACOSS_LAUNCH_CHECK();
+    if (int rc = ef_launch_rowbin_snf(cr, ld, E, P, (int)K, kappa, Wb, wplane, s)) return rc;
     if (binarize == ACOSS_EF_BIN_MUTUAL)
       if (int rc = ef_launch_colpass_snf(cr, ld, E, P, (int)K, kappa, Wb, wplane, s)) return rc;
     if (binary_out)

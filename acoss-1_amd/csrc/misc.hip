@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "ef_select.hpp"
 #include "sw_internal.hpp"
 
 namespace acoss {
@@ -129,14 +130,9 @@ __global__ __launch_bounds__(256) void k_csm(const float* __restrict__ X, const 
 
 // ---------------------------------------------------------------------------------------
 // csm_to_binary: the nn smallest of every row -> 1 (ties: lowest column first).
-// One wave per row; order-preserving u32 keys of the floats; lane l holds columns
-// [l*KPL, (l+1)*KPL) in registers (KPL*64 >= N) or reads the row in passes.
+// One wave per row, lane l columns [l * per, (l + 1) * per), the row read again in every
+// pass (wave_line_select_stream, ef_select.hpp); a byte per column. nn <= 0: all ones.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned fkey(float f) {
-  const unsigned u = __builtin_bit_cast(unsigned, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(256) void k_binarize_rows(const float* __restrict__ D, int M, int N, int nn,
                                                        uint8_t* __restrict__ B) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -150,37 +146,7 @@ __global__ __launch_bounds__(256) void k_binarize_rows(const float* __restrict__
   }
   const int per = (N + 63) / 64;  // columns per lane (chunked)
   const int c0 = lane * per, c1 = min(N, c0 + per);
-  // kth = smallest key with count(key <= kth) >= nn
-  unsigned a = 0, b = 0xffffffffu;
-  while (a < b) {
-    const unsigned mid = a + ((b - a) >> 1);
-    int c = 0;
-    for (int k = c0; k < c1; ++k) c += fkey(x[k]) <= mid;
-    if (wave_sum(c) >= nn)
-      b = mid;
-    else
-      a = mid + 1;
-  }
-  const unsigned kth = a;
-  int less = 0, eq = 0;
-  for (int k = c0; k < c1; ++k) {
-    const unsigned kk = fkey(x[k]);
-    less += kk < kth;
-    eq += kk == kth;
-  }
-  const int less_all = wave_sum(less);
-  const int take_eq = nn - less_all;  // equal keys taken in column order
-  const int eq_before = wave_incl_scan(eq) - eq;
-  int seen = eq_before;
-  for (int k = c0; k < c1; ++k) {
-    const unsigned kk = fkey(x[k]);
-    uint8_t v = kk < kth;
-    if (kk == kth) {
-      v = seen < take_eq;
-      ++seen;
-    }
-    o[k] = v;
-  }
+  wave_line_select_stream([&](int k) { return fkey_f32(x[k]); }, c0, c1, nn, [&](int k, bool v) { o[k] = v; });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -690,7 +690,7 @@ int acoss_earlyfusion_snf(const float* mfcc, const float* ssm, const float* chro
 /* acoss_earlyfusion, acoss_earlyfusion_locate and acoss_earlyfusion_path with `binarize` (one of
  * the two values above; anything else: ACOSS_E_ARG) directly after mu; everything else as the
  * twin, which forwards here with ACOSS_EF_BIN_ROWS. Under ACOSS_EF_BIN_MUTUAL the column pass
- * (csrc/ef_mutual.hip) runs after each row-binarise launch, over the three CSM planes before the
+ * (csrc/ef_binarize.hip) runs after each row-binarise launch, over the three CSM planes before the
  * fusion overwrites the first, and over the early matrix; with ACOSS_EF_BIN_ROWS nothing new runs. */
 int acoss_earlyfusion2(const float* mfcc, const float* ssm, const float* chroma, const float* chroma_med,
                        const int64_t* block_off, const int32_t* n_blocks, int32_t n_tracks, int32_t max_blocks,

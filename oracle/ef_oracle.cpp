@@ -17,7 +17,7 @@
 //
 // The reference computes the CSMs with numpy BLAS products, whose float32 summation order is
 // unspecified (and differs between BLAS builds). This restatement fixes ONE order, the one the
-// HIP kernels (earlyfusion.hip) follow, so the two can be compared with ==; np_oracle's
+// HIP kernels (ef_csm.hip) follow, so the two can be compared with ==; np_oracle's
 // BLAS-order composition (golden-pinned get_csm / get_csm_cosine) checks it within float32
 // tolerance (tests/test_ef_oracle.py). Canonical arithmetic, float32 unless noted:
 //   row norm   s_l = sum_{c = l mod 64} (x[c] * x[c]) sequential per l < 64 (product rounded,

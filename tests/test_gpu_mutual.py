@@ -1,4 +1,4 @@
-"""EarlyFusion's mutual nearest-neighbour binarisation on the GPU (csrc/ef_mutual.hip) against the
+"""EarlyFusion's mutual nearest-neighbour binarisation on the GPU (csrc/ef_binarize.hip) against the
 numpy restatement of the definition (mutual_np.py; include/acoss_hip.h, "mutual"). Every comparison
 is exact (==).
 
@@ -32,8 +32,8 @@ K, KAPPA, MU = ec.BANK_K, ec.BANK_KAPPA, 0.5
 # (rows, cols) per batch: max_rows / max_cols of a batch choose the row and the column class
 BATCHES = {
     1: [(1, 1), (1, 7), (7, 1), (4, 30), (30, 4), (15, 17), (16, 16), (17, 15), (33, 64), (64, 33), (64, 64)],
-    2: [(65, 64), (64, 65), (130, 70), (70, 130), (257, 300), (512, 40)],
-    3: [(600, 40), (40, 600), (513, 520)],
+    2: [(65, 64), (64, 65), (130, 70), (70, 130), (257, 300), (512, 40), (40, 512)],
+    3: [(600, 40), (40, 600), (513, 520), (1024, 40), (40, 1024)],
     4: [(1030, 40), (40, 1030)],
 }
 

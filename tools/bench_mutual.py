@@ -20,7 +20,9 @@ by a device synchronisation; a spread is min..max.
              without (this tree's wrappers; early SNF on the first --snf-pairs* pairs of the list).
   unchanged  with --parent-lib: acoss_earlyfusion, _locate, _path and _snf of both libraries,
              alternately on the same buffers: the same output bits, and whether each median lies
-             within the larger of the two spreads of its parent's.
+             within the larger of the two spreads of its parent's. Where the parent's library exports
+             the entries ending in 2, also those four with ACOSS_EF_BIN_MUTUAL, and the "binarize"
+             phase of acoss_earlyfusion2 in both modes, under the same rule.
   density    ones in the four masks of a sample of pairs, row rule against mutual
              (acoss_binarize_mutual on the matrices EarlyFusion.pair_matrices forms).
   map        MAP and MR1 of the five scores on bench_early_snf.py's synthetic covers80-shaped
@@ -55,25 +57,37 @@ def _summary(v, unit="s"):
             "all_" + unit: [round(x, 6) for x in v]}
 
 
-def _alternate(a, fns):
-    """{name: [seconds]} and the last outputs: the calls alternating, the order swapping every round."""
-    import torch
-    times, got = {k: [] for k in fns}, {}
-    names = list(fns)
+def _rounds(a, names, measure):
+    """{name: [measure(name) of each timed round]}: the calls alternating, the order swapping every round."""
+    got = {k: [] for k in names}
     for it in range(a.warmup + a.repeats):
         for k in (names if it % 2 == 0 else names[::-1]):
-            s, got[k] = _timed(fns[k], torch)
+            v = measure(k)
             if it >= a.warmup:
-                times[k].append(s)
-    return times, got
+                got[k].append(v)
+    return got
+
+
+def _alternate(a, fns):
+    """{name: [seconds]} and the last outputs of the alternating calls."""
+    import torch
+    got = {}
+
+    def measure(k):
+        s, got[k] = _timed(fns[k], torch)
+        return s
+    return _rounds(a, list(fns), measure), got
+
+
+TWINS = ("acoss_earlyfusion", "acoss_earlyfusion_locate", "acoss_earlyfusion_path", "acoss_earlyfusion_snf")
 
 
 def _bind(path):
-    """The parent commit's library: it lacks the new entries, so only the four twins are bound."""
+    """The parent commit's library: the four twins, and the entries ending in 2 where it exports them."""
     from acoss import _lib
     lib = ctypes.CDLL(os.path.abspath(path))
-    for name in ("acoss_earlyfusion", "acoss_earlyfusion_locate", "acoss_earlyfusion_path", "acoss_earlyfusion_snf",
-                 "acoss_profile_enable", "acoss_profile_read"):
+    lib.has2 = all(hasattr(lib, name + "2") for name in TWINS)
+    for name in TWINS + tuple(n + "2" for n in TWINS if lib.has2) + ("acoss_profile_enable", "acoss_profile_read"):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = _lib.SIGNATURES[name], ctypes.c_int
     lib.acoss_profile_phase_name.restype = ctypes.c_char_p
@@ -118,13 +132,7 @@ def bar_stage(a, bank, d_pairs, parent, out):
     calls = {"ref": (ref, lambda: chk(ref.acoss_earlyfusion(*lead, _lib._ptr(sc["ref"]), _lib._stream()))),
              "mutual": (this, lambda: chk(this.acoss_earlyfusion2(*lead, 1, _lib._ptr(sc["mutual"]), _lib._stream()))),
              "rows2": (this, lambda: chk(this.acoss_earlyfusion2(*lead, 0, _lib._ptr(sc["rows2"]), _lib._stream())))}
-    ms = {k: [] for k in calls}
-    names = list(calls)
-    for it in range(a.warmup + a.repeats):
-        for k in (names if it % 2 == 0 else names[::-1]):
-            v = _phase_ms(calls[k][0], calls[k][1])
-            if it >= a.warmup:
-                ms[k].append(v)
+    ms = _rounds(a, list(calls), lambda k: _phase_ms(*calls[k]))
     sm = {k: _summary(v, "ms") for k, v in ms.items()}
     ratio = sm["mutual"]["median_ms"] / sm["ref"]["median_ms"]
     same = bool(torch.equal(sc["ref"], sc["rows2"]))
@@ -156,8 +164,18 @@ def calls_stage(a, bank, d_pairs, n_snf, out):
     return res["locate_scores_equal_score"]
 
 
+def _agree(sm, unit, same):
+    """The tool's rule for a pair of summaries: the same bits, the medians within the larger spread."""
+    md, lo, hi = "median_" + unit, "min_" + unit, "max_" + unit
+    spread = max(v[hi] - v[lo] for v in sm.values())
+    diff = sm["this"][md] - sm["parent"][md]
+    return {"parent": sm["parent"], "this": sm["this"], "spread_" + unit: round(spread, 6),
+            "median_difference_" + unit: round(diff, 6), "agree_within_spread": bool(abs(diff) <= spread),
+            "same_bits": same}
+
+
 def unchanged_stage(a, bank, d_pairs, n_snf, parent, out):
-    """The four existing entries, parent's library against this tree's, alternately on the same buffers."""
+    """The existing entries, parent's library against this tree's, alternately on the same buffers."""
     import torch
     from acoss import _lib
     libs = {"parent": parent, "this": _lib.load_library()}
@@ -168,31 +186,41 @@ def unchanged_stage(a, bank, d_pairs, n_snf, parent, out):
     new = lambda dt, *s: torch.zeros(s, dtype=dt, device="cuda")  # noqa: E731
     buf = {k: {"score": new(torch.float64, P, 4), "seg": new(torch.int32, P, 4, 4), "lens": new(torch.int32, P, 4),
                "cells": new(torch.int32, P, 4, cap, 2), "snf": new(torch.float64, n_snf)} for k in libs}
+    outputs = {"acoss_earlyfusion": ("score",), "acoss_earlyfusion_locate": ("score", "seg"),
+               "acoss_earlyfusion_path": ("score", "seg", "lens", "cells"), "acoss_earlyfusion_snf": ("snf",)}
+
+    def call(k, entry, mode=None):
+        """`entry` of library k; mode: the binarize argument of its twin ending in 2."""
+        b, p, st = buf[k], _lib._ptr, _lib._stream()
+        fn = getattr(libs[k], entry + ("" if mode is None else "2"))
+        m = () if mode is None else (mode,)
+        if entry == "acoss_earlyfusion":
+            rc = fn(*lead, *m, p(b["score"]), st)
+        elif entry == "acoss_earlyfusion_locate":
+            rc = fn(*lead, *m, p(b["score"]), p(b["seg"]), st)
+        elif entry == "acoss_earlyfusion_path":
+            rc = fn(*lead, *m, p(b["score"]), p(b["seg"]), cap, p(b["lens"]), p(b["cells"]), st)
+        else:  # acoss_earlyfusion_snf2 also takes binary_out before the stream
+            rc = fn(*lead_snf, *m, NITERS, 1.0, p(b["snf"]), None, 0, None, *(() if mode is None else (None,)), st)
+        if rc:
+            raise RuntimeError("%s (%s, mode %r) returned %d" % (entry, k, mode, rc))
+
+    def same(entry):
+        return all(bool(torch.equal(buf["parent"][q].view(torch.uint8), buf["this"][q].view(torch.uint8)))
+                   for q in outputs[entry])
+
     res, ok = {}, True
-    for entry in ("acoss_earlyfusion", "acoss_earlyfusion_locate", "acoss_earlyfusion_path", "acoss_earlyfusion_snf"):
-        def call(k, entry=entry):
-            b, p, st = buf[k], _lib._ptr, _lib._stream()
-            if entry == "acoss_earlyfusion":
-                rc = libs[k].acoss_earlyfusion(*lead, p(b["score"]), st)
-            elif entry == "acoss_earlyfusion_locate":
-                rc = libs[k].acoss_earlyfusion_locate(*lead, p(b["score"]), p(b["seg"]), st)
-            elif entry == "acoss_earlyfusion_path":
-                rc = libs[k].acoss_earlyfusion_path(*lead, p(b["score"]), p(b["seg"]), cap, p(b["lens"]), p(b["cells"]), st)
-            else:
-                rc = libs[k].acoss_earlyfusion_snf(*lead_snf, NITERS, 1.0, p(b["snf"]), None, 0, None, st)
-            if rc:
-                raise RuntimeError("%s (%s) returned %d" % (entry, k, rc))
-        times, _ = _alternate(a, {k: (lambda k=k: call(k)) for k in libs})
-        sm = {k: _summary(v) for k, v in times.items()}
-        spread = max(v["max_s"] - v["min_s"] for v in sm.values())
-        keys = {"acoss_earlyfusion": ("score",), "acoss_earlyfusion_locate": ("score", "seg"),
-                "acoss_earlyfusion_path": ("score", "seg", "lens", "cells"), "acoss_earlyfusion_snf": ("snf",)}[entry]
-        same = all(bool(torch.equal(buf["parent"][q].view(torch.uint8), buf["this"][q].view(torch.uint8))) for q in keys)
-        res[entry] = {"parent": sm["parent"], "this": sm["this"], "spread_s": round(spread, 6),
-                      "median_difference_s": round(sm["this"]["median_s"] - sm["parent"]["median_s"], 6),
-                      "agree_within_spread": bool(abs(sm["this"]["median_s"] - sm["parent"]["median_s"]) <= spread),
-                      "same_bits": same}
-        ok = ok and same
+    for mode in (None, 1) if parent.has2 else (None,):
+        for entry in TWINS:
+            times, _ = _alternate(a, {k: (lambda k=k: call(k, entry, mode)) for k in libs})
+            r = _agree({k: _summary(v) for k, v in times.items()}, "s", same(entry))
+            res[entry + ("" if mode is None else "2_mutual")] = r
+            ok = ok and r["same_bits"]
+    for tag, mode in (("rows", 0), ("mutual", 1)) if parent.has2 else ():
+        ms = _rounds(a, list(libs), lambda k: _phase_ms(libs[k], lambda: call(k, "acoss_earlyfusion", mode)))
+        r = _agree({k: _summary(v, "ms") for k, v in ms.items()}, "ms", same("acoss_earlyfusion"))
+        res["binarize_phase_earlyfusion2_" + tag] = r
+        ok = ok and r["same_bits"]
     out["unchanged"] = res
     return ok
 
