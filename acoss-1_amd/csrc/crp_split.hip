@@ -330,10 +330,17 @@ __device__ __forceinline__ void sweep_body_sys(const PairView& V, int p, int str
     for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(pq[k].x), "+v"(pq[k].y), "+v"(pq[k].z), "+v"(pq[k].w));
     __builtin_amdgcn_wave_barrier();  // the next block's tile writes stay behind these reads
     gu16* hcb = (gu16*)(Hc + ((size_t)strip * ldc + jb) * kSR);
+    // Nontemporal: nothing reads this plane before the column select, a whole sub-batch of planes
+    // (about 1 GB at 2,000 frames) later, while the block reads its row-major pieces back at once
+    // in the fused row select. Stored with the default policy, the strip-major half of the
+    // sweep's output takes cache from the half that is read back: sweep 0.447 -> 0.418 ms per
+    // sub-batch and the column select 0.245 -> 0.230 (profiles/sweep_tall/README.txt). The same
+    // hint on either select's loads measured worse.
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int t = lane + 64 * k;
-      if (t < kTilePieces && jb + (t >> 2) < V.Np) *(gu4*)((gchar*)hcb + (unsigned)t * 16u) = pq[k];
+      if (t < kTilePieces && jb + (t >> 2) < V.Np)
+        __builtin_nontemporal_store(pq[k], (gu4*)((gchar*)hcb + (unsigned)t * 16u));
     }
   }
   // kNone over [N', align32(N')) of every row: the row select's last 32-element run then needs
