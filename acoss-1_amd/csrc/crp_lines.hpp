@@ -424,9 +424,12 @@ struct LineS : Codes<KQ / 2, KQ == 16> {
   }
   // the n codes of a line; addr(e): where element e's code is. Every lane loads (elements past
   // the line re-read element n - 1 and are replaced by kNone): no per-element branches.
-  template <class AT>
+  // FRESH: the lane's element offsets are computed here, not shared with the caller's other loads
+  // (a rare reload then keeps none of them in registers meanwhile).
+  template <bool FRESH = false, class AT>
   __device__ __forceinline__ void load(AT addr, int n) {
-    const int lane = threadIdx.x & 63;
+    int lane = threadIdx.x & 63;
+    if (FRESH) asm volatile("" : "+v"(lane));
     this->no_window();
     unsigned v[KQ];
 #pragma unroll

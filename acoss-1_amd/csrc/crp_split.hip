@@ -466,6 +466,21 @@ __device__ __forceinline__ bool hist_next(const unsigned* hist, unsigned base, u
   return true;
 }
 
+// A wave's run of 8 consecutive rows defers the exact keys of its lines' tie groups: each row's
+// search leaves the groups' member cells and a record here, and one flush per run recomputes all
+// of them, ranks them and finishes the rows (run_flush). The column select keeps the per-line
+// form: batched, its short lines ran 23 % slower and its long ones the same
+// (profiles/select_batch/README.md).
+constexpr int kRunMax = 8;    // lines per run
+constexpr int kRunCap = 128;  // member cells a run's lists hold (two per lane)
+struct RunRec {
+  unsigned Pl, Ph;  // the prefix of rank lo; the next prefix with elements (g2 > 0 only)
+  int off, g1, g2;  // members of Pl's group at list[off, off + g1), of Ph's at [off + g1, off + g1 + g2)
+  int rho;          // rank of the lower order statistic inside Pl's group
+  int two;          // the upper one is rank rho + 1 of the same group (else, g2 > 0: the least key of Ph's)
+  int pad;
+};
+
 // Scratch of one wave in LDS: element list and 64 bit-words.
 struct alignas(16) WaveLds {
   int list[64];
@@ -473,6 +488,14 @@ struct alignas(16) WaveLds {
   uint32_t hist[128];   // the lines' prefix histogram (hist_rank)
   uint32_t sink[64];    // per-lane targets of the elements outside the histogram (hist_add)
   float gv[64 * kMS];  // Gram terms of a group's cells, [member][frame]
+};
+
+// A wave's run in LDS (row select only): the lists, keys and records.
+struct alignas(16) RunLds {
+  int blist[kRunCap];      // member cells: query frame | reference frame << 12 | line << 24 | second group << 27
+  unsigned bkey[kRunCap];  // their exact keys
+  RunRec rec[kRunMax];     // one record per line of the run
+  unsigned vlo[kRunMax], vhi[kRunMax], Tl[kRunMax];  // the lines' order statistics and thresholds T
 };
 
 // Exact keys of a prefix group (the line elements whose 16-bit prefix is P), computed in ONE
@@ -804,15 +827,31 @@ __device__ __forceinline__ void plan_threshold(const Plan& pl, unsigned vlo, uns
   *T = sq_threshold(th);
 }
 
-// Threshold (distance units) and squared-domain threshold of a line of n keys; leaves the
+// Threshold (distance units) and squared-domain threshold of a line from its plan; leaves the
 // exact keys of the last batched group in *cache for le_bits.
+template <class LT, class KF>
+__device__ __forceinline__ void plan_line_threshold(const LT& L, const Plan& pl, const KF& keyf, WaveLds& W, Group* c_lo,
+                                                    Group* c_hi, float* thr, float* T) {
+  unsigned vlo, vhi;
+  line_groups(L, pl, keyf, W, c_lo, c_hi, &vlo, &vhi);
+  plan_threshold(pl, vlo, vhi, thr, T);
+}
+
+// The same for a line of n keys, search included.
 template <class LT, class KF>
 __device__ __forceinline__ void line_threshold(const LT& L, int n, float kappa, const KF& keyf, WaveLds& W, Group* c_lo,
                                Group* c_hi, float* thr, float* T, Hint* hint) {
   const Plan pl = line_plan<LT, KF>(L, n, kappa, W, hint);
-  unsigned vlo, vhi;
-  line_groups(L, pl, keyf, W, c_lo, c_hi, &vlo, &vhi);
-  plan_threshold(pl, vlo, vhi, thr, T);
+  plan_line_threshold(L, pl, keyf, W, c_lo, c_hi, thr, T);
+}
+
+// The percentile's rank targets of a line of n keys (the same for every line of a run).
+__device__ __forceinline__ Plan plan_ranks(int n, float kappa) {
+  Plan pl;
+  pl.q = (float)(n - 1) * kappa;
+  pl.lo_f = floorf(pl.q);
+  pl.hi_f = ceilf(pl.q);
+  return pl;
 }
 
 // Bits of "key <= T" for this lane's elements (in the line type's bit order): every
@@ -855,15 +894,202 @@ __device__ __forceinline__ auto le_bits(const LT& L, unsigned Tbits, const KF& k
 }
 
 // ---------------------------------------------------------------------------------------
+// The run: search per line, recompute and finish once per run.
+// ---------------------------------------------------------------------------------------
+// Wave-uniform state of a run.
+struct Run {
+  int ntot;       // member cells listed so far
+  int maxg;       // the largest listed group
+  unsigned pend;  // bit c: line c of the run awaits the flush
+};
+
+// The end of a line's search when its exact keys can wait for the run's flush: the member cells of
+// Pl's group (and of the next group, when the upper order statistic is its least key) go to the
+// run's lists, the line's le_mask(Pl) word per lane to lew (the flush corrects it into the
+// "key <= T" word), a record to B.rec[c]. False, nothing written: a group above 64 members (the
+// histogram ranks of big_group_rank) or lists that would overflow; the caller settles the line in
+// place (line_groups, le_bits), which touches none of the run's LDS.
+template <class LT, class KF>
+__device__ __forceinline__ bool line_defer(const LT& L, const Plan& pl, int c, const KF& keyf, RunLds& B, Run& R,
+                                           uint32_t* lew) {
+  const int lane = threadIdx.x & 63;
+  const int g1 = pl.le - pl.less;
+  const bool straddle = pl.hi != pl.lo && pl.hi >= pl.le;
+  unsigned Ph = 0u;
+  int g2 = 0;
+  if (g1 > 64) return false;
+  if (straddle) {
+    if (pl.next_ok) {
+      Ph = pl.Ph2;
+      g2 = pl.gh2;
+    } else {
+      Ph = L.min_greater(pl.Pl);
+      g2 = L.count_le(Ph) - pl.le;
+    }
+  }
+  if (g2 > 64 || R.ntot + g1 + g2 > kRunCap) return false;
+  const int ebase = L.ebase();
+  auto m1 = L.eq_mask(pl.Pl);
+  decltype(m1) m2 = 0;
+  if (g2 > 0) m2 = L.eq_mask(Ph);
+  const int c1 = popc(m1), c2 = popc(m2);
+  const int packed = c1 | (c2 << 16);  // per-lane counts <= 64: one scan for both lists
+  const int sc = wave_incl_scan(packed) - packed;
+  int i1 = R.ntot + (sc & 0xffff), i2 = R.ntot + g1 + (sc >> 16);
+  const int tag = c << 24;
+  while (m1) {
+    const int e = L.elem(ebase, ctz(m1));
+    B.blist[i1++] = keyf.qi(e) | (keyf.rj(e) << 12) | tag;
+    m1 &= m1 - 1;
+  }
+  while (m2) {
+    const int e = L.elem(ebase, ctz(m2));
+    B.blist[i2++] = keyf.qi(e) | (keyf.rj(e) << 12) | tag | (1 << 27);
+    m2 &= m2 - 1;
+  }
+  const auto word = L.le_mask(pl.Pl);  // kNone is never <= Pl
+  lew[lane] = (uint32_t)word;
+  if (LT::kHalves == 2) lew[64 + lane] = (uint32_t)((uint64_t)word >> 32);
+  if (lane == 0) B.rec[c] = RunRec{pl.Pl, Ph, R.ntot, g1, g2, pl.lo - pl.less, (pl.hi != pl.lo && !straddle) ? 1 : 0, 0};
+  R.ntot += g1 + g2;
+  R.maxg = max(R.maxg, max(g1, g2));
+  R.pend |= 1u << c;
+  return true;
+}
+
+// cell_key (at tau = 1, the only stacking this file is launched with) with the frame loads of NB
+// Gram terms issued together (9 / NB round trips per key instead of nine; 24 VGPRs per term in
+// flight): the same chains, the same sequential sum. The cell's 9 frame pairs are consecutive:
+// one address per track, the rest immediate offsets.
+template <int NB>
+__device__ __forceinline__ unsigned cell_key_run(const PairView& V, int i, int j) {
+  static_assert(kMS % NB == 0, "whole batches");
+  const float nq = V.NXq[i], nr = V.NXr[j];
+  const f32x4* x = reinterpret_cast<const f32x4*>(V.X + (size_t)i * 12);
+  const f32x4* y = reinterpret_cast<const f32x4*>(V.Yr + (size_t)j * 12);
+  float dot = 0.0f;
+#pragma unroll
+  for (int u0 = 0; u0 < kMS; u0 += NB) {
+    f32x4 xs[NB][3], ys[NB][3];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        xs[k][q] = x[3 * (u0 + k) + q];
+        ys[k][q] = y[3 * (u0 + k) + q];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      const float g = gram12(xs[k][0], xs[k][1], xs[k][2], ys[k][0], ys[k][1], ys[k][2]);
+      dot = (u0 + k == 0) ? g : dot + g;
+    }
+  }
+  const float d2 = (nq - 2.0f * dot) + nr;  // cell_finish
+  return __builtin_bit_cast(unsigned, d2 > 0.0f ? d2 : 0.0f);
+}
+
+// The flush of a run: (1) the exact keys of every listed cell, one lane per cell; (2) each cell's
+// rank inside its own group, all lines in one counting loop of maxg steps, and from the ranks the
+// lines' order statistics; (3) lane c finishes line c: percentile, T, both stored; (4) the le
+// words corrected: T's prefix is Pl (clear the members of Pl's group above T), Ph (set the members
+// of Ph's group at or below T), or lies between the two with no element there (the same two rules
+// change nothing); (5) any other T, e.g. one that fell an ulp under a key at the bottom of Pl:
+// reload(c, T) runs le_bits on the reloaded line. thr / Tq: the run's first line.
+template <class LT, int NB, class RL>
+__device__ __forceinline__ void run_flush(const PairView& V, const Run& R, const Plan& pq, RunLds& B, uint32_t* lew,
+                                          int lstride, float* thr, float* Tq, RL reload) {
+  if (R.pend == 0u) return;
+  const int lane = threadIdx.x & 63;
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+  for (int m0 = 0; m0 < R.ntot; m0 += 64) {
+    const int m = m0 + lane;
+    const int ent = B.blist[m < R.ntot ? m : 0];  // lanes past the lists: cell 0, a valid one
+    B.bkey[m] = cell_key_run<NB>(V, ent & 0xfff, (ent >> 12) & 0xfff);
+  }
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+  for (int m0 = 0; m0 < R.ntot; m0 += 64) {
+    const int m = m0 + lane;
+    const bool act = m < R.ntot;
+    const int ent = B.blist[act ? m : 0];
+    const unsigned key = B.bkey[act ? m : 0];
+    const int c = (ent >> 24) & 7;
+    const bool second = (ent >> 27) & 1;
+    const RunRec rc = B.rec[c];
+    const int gs = second ? rc.off + rc.g1 : rc.off, gn = second ? rc.g2 : rc.g1;
+    int cl = 0, ce = 0;
+#pragma unroll 4
+    for (int k = 0; k < R.maxg; ++k) {
+      const unsigned o = B.bkey[min(gs + k, kRunCap - 1)];
+      const bool in = k < gn;
+      cl += in && o < key;
+      ce += in && o == key;
+    }
+    if (act) {  // (tied members store the same key)
+      if (!second) {
+        if (cl <= rc.rho && rc.rho < cl + ce) B.vlo[c] = key;
+        if (rc.two && cl <= rc.rho + 1 && rc.rho + 1 < cl + ce) B.vhi[c] = key;
+      } else if (cl == 0) {
+        B.vhi[c] = key;
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  unsigned long long bad;
+  {
+    const bool mine = lane < kRunMax && ((R.pend >> lane) & 1u);
+    const int c = mine ? lane : __builtin_ctz(R.pend);
+    const RunRec rc = B.rec[c];
+    float th, T;
+    plan_threshold(pq, B.vlo[c], B.vhi[c], &th, &T);  // (vhi unused when q is an integer)
+    const unsigned T16 = __builtin_bit_cast(unsigned, T) >> 16;
+    const bool ok = T16 == rc.Pl || (rc.g2 > 0 && T16 > rc.Pl && T16 <= rc.Ph);
+    if (mine) {
+      thr[lane] = th;
+      Tq[lane] = T;
+      B.Tl[lane] = __builtin_bit_cast(unsigned, T);
+    }
+    bad = __ballot(mine && !ok);
+  }
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+  for (int m0 = 0; m0 < R.ntot; m0 += 64) {
+    const int m = m0 + lane;
+    const bool act = m < R.ntot;
+    const int ent = B.blist[act ? m : 0];
+    const unsigned key = B.bkey[act ? m : 0];
+    const int c = (ent >> 24) & 7;
+    const bool second = (ent >> 27) & 1;
+    const unsigned Tb = B.Tl[c];
+    const int e = (ent >> 12) & 0xfff;  // a row's element: the reference frame
+    uint32_t* word = lew + c * lstride + LT::lane_of(e);
+    const uint32_t bit = 1u << LT::bit_of(e);
+    if (act && !second && key > Tb) atomicAnd(word, ~bit);
+    if (act && second && key <= Tb) atomicOr(word, bit);
+  }
+  __builtin_amdgcn_wave_barrier();
+  while (bad) {  // wave-uniform
+    const int c = __builtin_ctzll(bad);
+    bad &= bad - 1;
+    reload(c, (unsigned)__builtin_amdgcn_readfirstlane((int)B.Tl[c]));
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---------------------------------------------------------------------------------------
 // k_sel_rows9: one 512-thread block per (32-row strip, pair); wave w takes rows w, w+8, ...
 // Emits T_row and the strip's row-threshold words RT[strip][j] (bit r: key(i0+r, j) <= T_row).
 // ---------------------------------------------------------------------------------------
 // LDS of the fused row select: one WaveLds per wave and the strip's row bits
-constexpr int kRowsLds = 4 * (int)sizeof(WaveLds) + kSR * 64 * 4;
+constexpr int kRowsLds = 4 * (int)(sizeof(WaveLds) + sizeof(RunLds)) + kSR * 64 * 4;
 // launches with lines past 2048 codes: row bits of 128 words per row
-constexpr int kRowsLds2 = 4 * (int)sizeof(WaveLds) + kSR * 128 * 4;
+constexpr int kRowsLds2 = 4 * (int)(sizeof(WaveLds) + sizeof(RunLds)) + kSR * 128 * 4;
 // the sweep phase's four staging tiles share this LDS (one union, the phases a block barrier apart)
 static_assert(4 * kTileBytes <= kRowsLds, "the sweep's staging tiles must fit the row select's LDS");
+// a CU's 160 KB: five blocks of the all-short launch, four of every other
+static_assert(5 * kRowsLds <= 160 * 1024 && 4 * kRowsLds2 <= 160 * 1024, "sweep blocks per CU by LDS");
 
 // In-register transpose of a 32 x 32 bit matrix: a[r] bit q -> a[q] bit r (stage J swaps the
 // off-diagonal J x J sub-blocks).
@@ -903,19 +1129,20 @@ struct LineOf<2> {
   using T = Line2;
 };
 
-template <int NW, int KQ, int RB>
+template <int NW, int KQ, int RB, int NB>
 __device__ __forceinline__ void rows_body(const PairView& V, int p, int strip, const uint16_t* Hr, int ldr,
                                           float kappa, float* __restrict__ thr,
                                           float* __restrict__ Tq, int64_t thr_stride, uint32_t* __restrict__ RT,
-                                          int64_t rt_stride, int ld, WaveLds* wl, uint32_t (*rowbits)[RB]) {
+                                          int64_t rt_stride, int ld, WaveLds* wl, RunLds* rl, uint32_t (*rowbits)[RB]) {
   using LT = typename LineOf<KQ>::T;
   const int i0 = strip * kSR;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // w: wave-uniform (SGPR)
   WaveLds& W = wl[w];
+  RunLds& B = rl[w];
   constexpr int RPW = kSR / NW;  // consecutive rows per wave: each search starts from its neighbour's
   Hint hint{kNoHint, 1.0f};
   // the next row's line is loaded while this one is searched (its latency hidden)
-  auto load_row = [&](LT& Ld, int i) {
+  auto load_row = [&](LT& Ld, int i, auto fresh) {
     int64_t rowoff = (int64_t)(i - i0) * ldr;
     asm volatile("" : "+s"(rowoff));  // per-row address: nothing per lane hoisted out of the loop
     if constexpr (KQ == 0) {
@@ -925,13 +1152,19 @@ __device__ __forceinline__ void rows_body(const PairView& V, int p, int strip, c
       Ld.B.template load_lanes<false>(Hr + rowoff + 2048, 32, V.Np - 2048);
     } else {
       const uint16_t* row = Hr + rowoff;
-      Ld.load([&](int e) { return row + (unsigned)e; }, V.Np);
+      Ld.template load<decltype(fresh)::value>([&](int e) { return row + (unsigned)e; }, V.Np);
     }
   };
   // Line2 loads each line when it starts (no prefetch: 48 VGPRs, the 4th wave per SIMD)
   constexpr bool kPF = KQ != 2;
   // one row's select on its loaded line L; prefetch() requests the wave's next line once this
   // one's window is built
+  // The wave's rows are one run: a row's search leaves its le words (the line type's lane and bit
+  // order) in rowbits[r] and its tie groups in the run's lists; rows whose groups cannot wait are
+  // settled here, as a single line.
+  static_assert(RPW <= kRunMax, "a wave's rows are one run");
+  const int r0 = w * RPW, r1 = (w + 1) * RPW;
+  Run R{0, 0, 0u};
   auto row = [&](LT& L, int r, auto&& prefetch) {
     const int i = i0 + r;
     uint64_t word = 0;  // (Line2: the second half's word in bits 32..63)
@@ -942,26 +1175,26 @@ __device__ __forceinline__ void rows_body(const PairView& V, int p, int strip, c
       }
       prefetch();
       const LineCells<true> keyf{V, i};
+      const Plan pl = line_plan<LT, LineCells<true>>(L, V.Np, kappa, W, &hint);
+      if (line_defer(L, pl, r - r0, keyf, B, R, &rowbits[r][0])) return;
       float th, T;
       Group c_lo, c_hi;
       c_lo.g = c_hi.g = -1;
-      line_threshold(L, V.Np, kappa, keyf, W, &c_lo, &c_hi, &th, &T, &hint);
+      plan_line_threshold(L, pl, keyf, W, &c_lo, &c_hi, &th, &T);
       if (lane == 0) {
         thr[(size_t)p * thr_stride + i] = th;
         Tq[(size_t)p * thr_stride + i] = T;
       }
       word = le_bits(L, __builtin_bit_cast(unsigned, T), keyf, W, c_lo, c_hi);
-      if constexpr (KQ == 8 || KQ == 16) word = lane_words<KQ>((uint32_t)word);  // lane t: columns 32t .. 32t + 31
     }
     rowbits[r][lane] = (uint32_t)word;
     if constexpr (KQ == 2) rowbits[r][64 + lane] = (uint32_t)(word >> 32);
   };
   // (unrolled by two for long lines, each line in its own registers instead of the copy of the
   // prefetched line: neutral, profiles/r04/ab_unroll2000.txt)
-  const int r1 = (w + 1) * RPW;
   {
     LT Lnext;
-    if (kPF && i0 + w * RPW < V.Mp) load_row(Lnext, i0 + w * RPW);
+    if (kPF && i0 + w * RPW < V.Mp) load_row(Lnext, i0 + w * RPW, std::false_type{});
 #pragma unroll 1
     for (int r = w * RPW; r < r1; ++r) {
       LT L;
@@ -969,11 +1202,33 @@ __device__ __forceinline__ void rows_body(const PairView& V, int p, int strip, c
         if constexpr (kPF)
           L = Lnext;
         else
-          load_row(L, i0 + r);
+          load_row(L, i0 + r, std::false_type{});
       }
       row(L, r, [&] {
-        if (kPF && r + 1 < r1 && i0 + r + 1 < V.Mp) load_row(Lnext, i0 + r + 1);
+        if (kPF && r + 1 < r1 && i0 + r + 1 < V.Mp) load_row(Lnext, i0 + r + 1, std::false_type{});
       });
+    }
+  }
+  {
+    // (an opaque copy: the rank targets are recomputed here, not kept in VGPRs across the flush)
+    float kap = kappa;
+    asm volatile("" : "+s"(kap));
+    const Plan pq = plan_ranks(V.Np, kap);
+    float* thr0 = thr + (size_t)p * thr_stride + i0 + r0;
+    float* Tq0 = Tq + (size_t)p * thr_stride + i0 + r0;
+    run_flush<LT, NB>(V, R, pq, B, &rowbits[r0][0], RB, thr0, Tq0, [&](int c, unsigned Tbits) {
+      LT L;
+      load_row(L, i0 + r0 + c, std::true_type{});
+      const LineCells<true> keyf{V, i0 + r0 + c};
+      Group c_lo, c_hi;
+      c_lo.g = c_hi.g = -1;
+      const uint64_t word = le_bits(L, Tbits, keyf, W, c_lo, c_hi);
+      rowbits[r0 + c][lane] = (uint32_t)word;
+      if constexpr (KQ == 2) rowbits[r0 + c][64 + lane] = (uint32_t)(word >> 32);
+    });
+    if constexpr (KQ == 8 || KQ == 16) {  // lane t: columns 32t .. 32t + 31
+#pragma unroll 1
+      for (int r = r0; r < r1; ++r) rowbits[r][lane] = lane_words<KQ>(rowbits[r][lane]);
     }
   }
   __syncthreads();
@@ -1044,6 +1299,7 @@ constexpr int kSweepLds = KQ == 2 ? kRowsLds2 : kRowsLds;
 template <int KQ>
 __device__ __forceinline__ void sweep_rows_block(const SweepArgs& A, int strip, int p, char* smem) {
   constexpr int RB = KQ == 2 ? 128 : 64;  // row-bit words per row
+  constexpr int NB = KQ == 8 ? 1 : 3;     // Gram terms in flight per key of a flush (96 / 128 VGPRs)
   const CrpBatch& B = A.B;
   const KeyPlanes& K = A.K;
   const int ldr = A.ldr, ldc = A.ldc, ld = A.ld, short_n = A.short_n;
@@ -1062,18 +1318,19 @@ __device__ __forceinline__ void sweep_rows_block(const SweepArgs& A, int strip, 
     sweep_body_sys<true>(V, p, strip, K, ldr, ldc, kstride, Hr, smem);
   __syncthreads();  // the strip's F rows are complete (block-scope visibility of the global stores)
   WaveLds* wl = reinterpret_cast<WaveLds*>(smem);
-  uint32_t(*rowbits)[RB] = reinterpret_cast<uint32_t(*)[RB]>(smem + 4 * sizeof(WaveLds));
+  RunLds* rl = reinterpret_cast<RunLds*>(smem + 4 * sizeof(WaveLds));
+  uint32_t(*rowbits)[RB] = reinterpret_cast<uint32_t(*)[RB]>(smem + 4 * (sizeof(WaveLds) + sizeof(RunLds)));
   // lines of <= short_n codes take LineS<8> in every launch type but KQ = 8 (all short); KQ = 16
   // launches (every line <= 1024 codes) take LineS<16> for the rest (a third select type in a
   // KQ = 0 launch costs more than it saves)
   if (KQ == 8 || V.Np <= short_n)
-    rows_body<4, 8, RB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rowbits);
+    rows_body<4, 8, RB, NB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rl, rowbits);
   else if (KQ == 16)
-    rows_body<4, 16, RB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rowbits);
+    rows_body<4, 16, RB, NB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rl, rowbits);
   else if (KQ == 2 && V.Np > 2048)
-    rows_body<4, 2, RB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rowbits);
+    rows_body<4, 2, RB, NB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rl, rowbits);
   else
-    rows_body<4, 0, RB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rowbits);
+    rows_body<4, 0, RB, NB>(V, p, strip, Hr, ldr, kappa, thr, Tq, thr_stride, RT, rt_stride, ld, wl, rl, rowbits);
 }
 
 template <int KQ>
