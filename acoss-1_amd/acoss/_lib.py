@@ -43,6 +43,18 @@ class CrpParams2(ctypes.Structure):
         raise AttributeError(name)
 
 
+class CrpParams3(ctypes.Structure):
+    """acoss_crp_params3 — acoss_crp_params2 and the ranked OTI (include/acoss_hip.h): what the entries
+    ending in 3 take. n_oti is read by acoss_crp_align3 alone; oti_pick is the scalar pick of the
+    others. m, tau, ..., binarize and oti_rank read through to the base."""
+    _fields_ = [("base", CrpParams2), ("n_oti", ctypes.c_int32), ("oti_pick", ctypes.c_int32)]
+
+    def __getattr__(self, name):  # only reached for what the struct itself does not have
+        if name in ("m", "tau", "kappa", "oti", "gamma_open", "gamma_ext", "binarize", "oti_rank"):
+            return getattr(self.base, name)
+        raise AttributeError(name)
+
+
 class NpzMember(ctypes.Structure):
     """acoss_npz_member — one array of an .npz feature file (include/acoss_hip.h)."""
     _fields_ = [("file", ctypes.c_int32), ("method", ctypes.c_int32), ("ndim", ctypes.c_int32),
@@ -121,6 +133,15 @@ for _name in ("acoss_crp_align", "acoss_crp_locate", "acoss_crp_locate_dmax", "a
     SIGNATURES[_name + "2"] = [ctypes.POINTER(CrpParams2) if a is ctypes.POINTER(CrpParams) else a
                                for a in SIGNATURES[_name]]
 SIGNATURES["acoss_crp_pair2"] = [_vp, _i32, _vp, _i32, ctypes.POINTER(CrpParams2), _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+# the entries ending in 3: acoss_crp_params3, and the pick plane before the stream; acoss_crp_align3 has two
+# shifts and two picks where acoss_crp_align2 has oti_out
+for _name in ("acoss_crp_locate", "acoss_crp_locate_dmax", "acoss_crp_path", "acoss_crp_path_dmax", "acoss_crp_rqa"):
+    SIGNATURES[_name + "3"] = [ctypes.POINTER(CrpParams3) if a is ctypes.POINTER(CrpParams) else a
+                               for a in SIGNATURES[_name][:-1]] + [_vp, _vp]
+SIGNATURES["acoss_crp_align3"] = [_vp, _vp, _vp, _i32, _i32, _vp, _i64, ctypes.POINTER(CrpParams3), _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp]
+SIGNATURES["acoss_crp_pair3"] = [_vp, _i32, _vp, _i32, ctypes.POINTER(CrpParams3), _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+SIGNATURES["acoss_oti_ranked"] = [_vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]
 # EarlyFusion's entries ending in 2: int32 binarize (EF_BINARIZE) directly after mu; acoss_earlyfusion_snf2
 # also gains binary_out before the stream
 for _name in ("acoss_earlyfusion", "acoss_earlyfusion_locate", "acoss_earlyfusion_path", "acoss_earlyfusion_snf"):
@@ -260,6 +281,34 @@ def binarize_suffix(binarize="percentile", oti_rank=1):
     return "-otib" if oti_rank == 1 else "-otib%d" % oti_rank
 
 
+def check_n_oti(n_oti, oti=True):
+    """The n_oti every layer takes: how many of the ranked transpositions are aligned, the best kept
+    (include/acoss_hip.h, acoss_crp_params3): an integer in 1 .. 12, and 1 without oti. Returns it as
+    an int; raises ValueError otherwise."""
+    if isinstance(n_oti, bool) or int(n_oti) != n_oti or not 1 <= int(n_oti) <= 12:
+        raise ValueError("n_oti must be an integer in 1 .. 12, not %r" % (n_oti,))
+    if int(n_oti) > 1 and not oti:
+        raise ValueError("n_oti = %d needs oti=True: without the OTI there is no ranking" % int(n_oti))
+    return int(n_oti)
+
+
+def n_oti_suffix(n_oti=1, oti=True):
+    """What a cache or result name carries for best of n: '' at 1, '-oti<n>' above. It follows the
+    binarize suffix and precedes the measure: Serra09-otib2-oti2-det."""
+    n_oti = check_n_oti(n_oti, oti)
+    return "" if n_oti == 1 else "-oti%d" % n_oti
+
+
+def crp_params3(params, n_oti=1, oti_pick=0):
+    """acoss_crp_params3 around crp_params(...)'s struct: the crp_* calls below then take the entries
+    ending in 3."""
+    if isinstance(params, CrpParams3):
+        params = params.base
+    if not isinstance(params, CrpParams2):
+        params = CrpParams2(params, BINARIZE["percentile"], 1)
+    return CrpParams3(params, int(n_oti), int(oti_pick))
+
+
 def crp_params(m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, binarize="percentile", oti_rank=1):
     """acoss_crp_params for the percentile CRP, acoss_crp_params2 for binarize='oti': the crp_* calls
     below pick the entry point (acoss_crp_align or acoss_crp_align2, ...) by the struct's type."""
@@ -269,8 +318,47 @@ def crp_params(m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5,
 
 
 def _entry(name, params):
-    """The library entry `name` for these params: its twin ending in 2 for acoss_crp_params2."""
-    return name + "2" if isinstance(params, CrpParams2) else name
+    """The library entry `name` for these params: its twin ending in 2 for acoss_crp_params2, in 3
+    for acoss_crp_params3."""
+    return name + ("3" if isinstance(params, CrpParams3) else "2" if isinstance(params, CrpParams2) else "")
+
+
+def _picked(params, picks, P):
+    """(params, device pick plane or None) of a crp_locate / crp_path / crp_rqa call: a pick plane
+    ((P,) int32, one rank of the ranked OTI per pair) takes the entry ending in 3."""
+    if picks is None:
+        return params, None
+    torch = _torch()
+    picks = _dev(picks, torch.int32).reshape(-1)
+    if int(picks.shape[0]) != P:
+        raise ValueError("picks has %d entries for %d pairs" % (int(picks.shape[0]), P))
+    return (params if isinstance(params, CrpParams3) else crp_params3(params)), picks
+
+
+def _n_pairs(pairs):
+    """The number of pairs of a (P, 2) tensor, array or list."""
+    if hasattr(pairs, "shape") and len(pairs.shape) == 2:
+        return int(pairs.shape[0])
+    return int(np.asarray(pairs).size // 2)
+
+
+def oti_ranked(feats, track_off, track_len, pairs, dots=True):
+    """The ranked OTI of every pair (acoss_oti_ranked): {"shifts" (P, 12) i32, the twelve shifts by
+    descending profile dot, ties to the smaller shift, shifts[:, 0] the OTI; with dots "dots" (P, 12)
+    f32, the dot of every shift}."""
+    torch = _torch()
+    feats = _dev(feats, torch.float32)
+    track_off = _dev(track_off, torch.int64)
+    track_len = _dev(track_len, torch.int32)
+    pairs, _ = _pairs_dev(pairs, int(track_len.shape[0]))
+    P = int(pairs.shape[0])
+    out = {"shifts": _empty("int32", P, 12)}
+    if dots:
+        out["dots"] = _empty("float32", P, 12)
+    rc = load_library().acoss_oti_ranked(_ptr(feats), _ptr(track_off), _ptr(track_len), int(track_len.shape[0]),
+                                         _ptr(pairs), P, _ptr(out["shifts"]), _ptr(out.get("dots")), _stream())
+    _check(rc, "acoss_oti_ranked")
+    return out
 
 
 # ----------------------------------------------------------------------------------------
@@ -307,9 +395,30 @@ def _empty(dtype, *shape):
     return torch.empty(shape, dtype=getattr(torch, dtype), device="cuda")
 
 
-def crp_align(feats, track_off, track_len, max_len, pairs, params, qmax=True, dmax=False, oti=False):
+def crp_align(feats, track_off, track_len, max_len, pairs, params, qmax=True, dmax=False, oti=False, n_oti=1):
     """Batched Serra09/Chen path. feats (sum_n, 12) f32, track_off (T,) i64, track_len (T,) i32,
-    pairs (P, 2) i32 (query, reference) -> dict of device tensors."""
+    pairs (P, 2) i32 (query, reference) -> dict of device tensors.
+
+    n_oti > 1, or acoss_crp_params3 for params: best of n_oti ranked transpositions
+    (acoss_crp_align3). "qmax" / "dmax" are then the best scores, and each aligner asked for brings
+    the shift and the pick that won it: "oti" and "pick_q" for Qmax (also with oti=True alone),
+    "oti_d" and "pick_d" for dmax, (P,) i32 each."""
+    if n_oti != 1:
+        params = crp_params3(params, check_n_oti(n_oti, params.oti))
+    if isinstance(params, CrpParams3):
+        keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
+        out = {}
+        if qmax or oti:
+            out.update(oti=_empty("int32", P), pick_q=_empty("int32", P))
+        if qmax:
+            out["qmax"] = _empty("float32", P)
+        if dmax:
+            out.update(dmax=_empty("float32", P), oti_d=_empty("int32", P), pick_d=_empty("int32", P))
+        rc = load_library().acoss_crp_align3(*lead, _ptr(out.get("qmax")), _ptr(out.get("dmax")), _ptr(out.get("oti")),
+                                             _ptr(out.get("oti_d")), _ptr(out.get("pick_q")), _ptr(out.get("pick_d")),
+                                             _stream())
+        _check(rc, "acoss_crp_align3")
+        return out
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     want = (("qmax", qmax, "float32"), ("dmax", dmax, "float32"), ("oti", oti, "int32"))
     out = {key: _empty(dtype, P) for key, on, dtype in want if on}
@@ -331,14 +440,15 @@ def crp_pair(X, Y, params, dist=True):
     M, N = X.shape[0], Y.shape[0]
     Mp, Np = stacked_len(M, params.m, params.tau), stacked_len(N, params.m, params.tau)
     D = _empty("float32", Mp, Np) if dist else None
-    if isinstance(params, CrpParams2):
+    if isinstance(params, (CrpParams2, CrpParams3)):  # acoss_crp_pair3: at the pick params.oti_pick
+        entry = _entry("acoss_crp_pair", params)
         otib = params.binarize == BINARIZE["oti"]
         tr, tc = (None, None) if otib else (_empty("float32", Mp), _empty("float32", Np))
         C, o = _empty("uint8", Mp, Np), _empty("int32", 1)
         closer = _empty("uint8", Mp, Np) if otib else None
-        rc = lib.acoss_crp_pair2(_ptr(X), M, _ptr(Y), N, ctypes.byref(params), _ptr(D), _ptr(tr), _ptr(tc), _ptr(C),
+        rc = getattr(lib, entry)(_ptr(X), M, _ptr(Y), N, ctypes.byref(params), _ptr(D), _ptr(tr), _ptr(tc), _ptr(C),
                                  _ptr(o), _ptr(closer), _stream())
-        _check(rc, "acoss_crp_pair2")
+        _check(rc, entry)
         out = {"dist": D, "crp": C, "oti": o}
         out.update({"closer": closer} if otib else {"thr_row": tr, "thr_col": tc})
         return out
@@ -377,17 +487,21 @@ def dmax_path_bound(M, N):
     return 0 if M < 3 or N < 3 else 2 * (M + N) // 3 - 2
 
 
-def crp_locate(feats, track_off, track_len, max_len, pairs, params, align=0):
+def crp_locate(feats, track_off, track_len, max_len, pairs, params, align=0, picks=None):
     """Batched Qmax with its location (acoss_crp_locate): inputs as crp_align. Returns device tensors
     {"qmax" (P,) f32, "seg" (P, 4) i32 = (i0, j0, i1, j1) in stacked-frame rows / columns, (-1, -1, -1, -1)
     where Qmax is 0, "oti" (P,) i32}. align=1: the dmax (chen17) alignment instead
     (acoss_crp_locate_dmax), the score under "dmax"; its path may begin on an intermediate cell of a
-    (2, 1) or (1, 2) step, so i0 or j0 may be 1 (see crp_path)."""
+    (2, 1) or (1, 2) step, so i0 or j0 may be 1 (see crp_path). picks ((P,) int32, or
+    acoss_crp_params3 for params): the rank of the ranked OTI each pair is located at
+    (acoss_crp_locate3); "oti" is the shift applied."""
     key, entry = _aligner(align, "acoss_crp_locate")
+    params, picks = _picked(params, picks, _n_pairs(pairs))
     entry = _entry(entry, params)
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     out = {key: _empty("float32", P), "seg": _empty("int32", P, 4), "oti": _empty("int32", P)}
-    rc = getattr(load_library(), entry)(*lead, _ptr(out[key]), _ptr(out["seg"]), _ptr(out["oti"]), _stream())
+    tail = (_ptr(picks),) if isinstance(params, CrpParams3) else ()
+    rc = getattr(load_library(), entry)(*lead, _ptr(out[key]), _ptr(out["seg"]), _ptr(out["oti"]), *tail, _stream())
     _check(rc, entry)
     return out
 
@@ -417,7 +531,7 @@ def _compact_paths(lens, padded):
     return off, padded[keep].reshape(-1, 2)
 
 
-def crp_path(feats, track_off, track_len, max_len, pairs, params, align=0):
+def crp_path(feats, track_off, track_len, max_len, pairs, params, align=0, picks=None):
     """Batched Qmax with its whole alignment path (acoss_crp_path): inputs as crp_align. Returns device
     tensors {"qmax" (P,) f32, "seg" (P, 4) i32 and "oti" (P,) i32 as crp_locate, "path_off" (P + 1,)
     i64, "cells" (total, 2) i32}: the path of pair p is cells[path_off[p]:path_off[p + 1]], (i, j) in
@@ -427,10 +541,12 @@ def crp_path(feats, track_off, track_len, max_len, pairs, params, align=0):
     align=1: the dmax (chen17) alignment (acoss_crp_path_dmax), the score under "dmax". Its steps are
     (1, 1), (2, 1), (1, 2) and, exactly after the intermediate cell of a (2, 1) or (1, 2) step that
     is a hit, (1, 0) and (0, 1): non-decreasing in i and j, up to dmax_path_bound cells, and i0 or
-    j0 may be 1 (a path may begin on such an intermediate cell, which may lie in row or column 1)."""
+    j0 may be 1 (a path may begin on such an intermediate cell, which may lie in row or column 1).
+    picks: as crp_locate's (acoss_crp_path3)."""
     torch = _torch()
     lib = load_library()
     key, entry = _aligner(align, "acoss_crp_path")
+    params, picks = _picked(params, picks, _n_pairs(pairs))
     entry = _entry(entry, params)
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     pairs = keep[3]
@@ -445,7 +561,8 @@ def crp_path(feats, track_off, track_len, max_len, pairs, params, align=0):
         padded = torch.empty((n, cap, 2), dtype=torch.int32, device="cuda")
         rc = getattr(lib, entry)(*lead[:5], _ptr(pairs[a:a + n]), int(n), lead[7], _ptr(q[a:a + n]),
                                  _ptr(seg[a:a + n]), _ptr(o[a:a + n]), int(cap), _ptr(lens[a:a + n]), _ptr(padded),
-                                 _stream())
+                                 *((_ptr(None if picks is None else picks[a:a + n]),)
+                                   if isinstance(params, CrpParams3) else ()), _stream())
         _check(rc, entry)
         parts.append(_compact_paths(lens[a:a + n], padded)[1])
     off = torch.zeros(P + 1, dtype=torch.int64, device="cuda")
@@ -476,12 +593,15 @@ RQA_COUNTS = ("n_rec", "n_lines", "n_lines_min", "n_pts_min")  # columns of "cou
 RQA_STATS = ("rr", "det", "lmean", "entr")                      # columns of "stats"
 
 
-def crp_rqa(feats, track_off, track_len, max_len, pairs, params, lmin=2, smax=True, hist_cap=0, lines=True):
+def crp_rqa(feats, track_off, track_len, max_len, pairs, params, lmin=2, smax=True, hist_cap=0, lines=True,
+            picks=None):
     """Batched cross-recurrence quantification (acoss_crp_rqa; the definition: include/acoss_hip.h):
     inputs as crp_align. Returns device tensors {"counts" (P, 4) i64 = RQA_COUNTS, "lmax" (P,) i32,
     "stats" (P, 4) f64 = RQA_STATS, "oti" (P,) i32, with smax "smax" (P,) f32, with hist_cap > 0
     "hist" (P, hist_cap) i32, hist[p, l] = the number of diagonal lines of length l}. lines=False
-    leaves "counts", "lmax" and "stats" out and skips the line walk unless a histogram is asked for."""
+    leaves "counts", "lmax" and "stats" out and skips the line walk unless a histogram is asked for.
+    picks: as crp_locate's (acoss_crp_rqa3)."""
+    params, picks = _picked(params, picks, _n_pairs(pairs))
     keep, P, lead = _bank_args(feats, track_off, track_len, max_len, pairs, params)
     out = {"oti": _empty("int32", P)}
     if lines:
@@ -493,7 +613,8 @@ def crp_rqa(feats, track_off, track_len, max_len, pairs, params, lmin=2, smax=Tr
     entry = _entry("acoss_crp_rqa", params)
     rc = getattr(load_library(), entry)(*lead, int(lmin), _ptr(out.get("counts")), _ptr(out.get("lmax")),
                                         _ptr(out.get("stats")), _ptr(out.get("smax")), _ptr(out["oti"]), int(hist_cap),
-                                        _ptr(out.get("hist")), _stream())
+                                        _ptr(out.get("hist")),
+                                        *((_ptr(picks),) if isinstance(params, CrpParams3) else ()), _stream())
     _check(rc, entry)
     return out
 

@@ -25,16 +25,20 @@ class ChenFusion(ChromaBackedAlgorithm):
     _takes_candidates = False  # the fusion needs every pair's score
 
     @staticmethod
-    def algorithm_name(binarize="percentile", oti_rank=1):
+    def algorithm_name(binarize="percentile", oti_rank=1, n_oti=1):
         """The name of the Ds cache and the results: 'LateFusionChen' (the reference's), on the
-        OTI-binary CRP 'LateFusionChen-otib', 'LateFusionChen-otib<rank>' above rank 1."""
-        return "LateFusionChen" + _lib.binarize_suffix(binarize, oti_rank)
+        OTI-binary CRP 'LateFusionChen-otib', 'LateFusionChen-otib<rank>' above rank 1; best of
+        n_oti > 1 transpositions adds '-oti<n>'."""
+        return "LateFusionChen" + _lib.binarize_suffix(binarize, oti_rank) + _lib.n_oti_suffix(n_oti)
 
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='benchmark', oti=True, kappa=0.095,
-                 tau=1, m=9, downsample_fac=40, cachedir="cache", binarize="percentile", oti_rank=1):
-        """binarize, oti_rank: as Serra09's (both alignments then run on the OTI-binary CRP)."""
-        name = self.algorithm_name(binarize, oti_rank)
-        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac, binarize, oti_rank)
+                 tau=1, m=9, downsample_fac=40, cachedir="cache", binarize="percentile", oti_rank=1,
+                 n_oti=1):
+        """binarize, oti_rank: as Serra09's (both alignments then run on the OTI-binary CRP).
+        n_oti: as Serra09's; Qmax and dmax are each the best over the n_oti best transpositions, each
+        with its own winner, which localize and align_path find with one extra scoring pass."""
+        name = self.algorithm_name(binarize, oti_rank, _lib.check_n_oti(n_oti, oti))
+        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac, binarize, oti_rank, n_oti)
         CoverAlgorithm.__init__(self, dataset_csv, name=name, similarity_types=["qmax", "dmax"],
                                 datapath=datapath, shortname=shortname, cachedir=cachedir)
 

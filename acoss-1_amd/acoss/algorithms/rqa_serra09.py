@@ -24,8 +24,10 @@ __all__ = ["Serra09", "ChromaBackedAlgorithm"]
 class ChromaBackedAlgorithm(CoverAlgorithm):
     """Shared by Serra09 and ChenFusion: cached median-downsampled chroma + a device bank."""
 
-    def _init_chroma(self, chroma_type, oti, kappa, tau, m, downsample_fac, binarize="percentile", oti_rank=1):
+    def _init_chroma(self, chroma_type, oti, kappa, tau, m, downsample_fac, binarize="percentile", oti_rank=1,
+                     n_oti=1):
         self.oti_rank = _lib.check_binarize(binarize, oti_rank)
+        self.n_oti = _lib.check_n_oti(n_oti, oti)
         self.binarize = binarize
         self.oti = oti
         self.tau = tau
@@ -73,8 +75,21 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
                     oti_rank=self.oti_rank)
 
     def _score_dev(self, idxs, dmax=False):
+        """Qmax (and dmax) of the pairs, the best of the n_oti best transpositions; with n_oti > 1
+        also the winners: "oti", "pick_q" (and "oti_d", "pick_d")."""
         self.prepare()
-        return self._bank.crp_align(np.asarray(idxs, np.int32), qmax=True, dmax=dmax, **self._crp_kw())
+        return self._bank.crp_align(np.asarray(idxs, np.int32), qmax=True, dmax=dmax, n_oti=self.n_oti,
+                                    **self._crp_kw())
+
+    def _picks_kw(self, idxs, align=0):
+        """The picks= of a bank call that must run on the transposition that won the pairs' best of
+        n_oti: the Qmax winner (align 0; RQA and every measure), the dmax winner (align 1). One more
+        scoring pass over the pairs; nothing at n_oti = 1."""
+        if self.n_oti == 1:
+            return {}
+        r = self._bank.crp_align(np.asarray(idxs, np.int32).reshape(-1, 2), qmax=not align, dmax=bool(align),
+                                 n_oti=self.n_oti, **self._crp_kw())
+        return {"picks": r["pick_d" if align else "pick_q"]}
 
     def _score(self, idxs, dmax=False):
         return {k: v.cpu().numpy() for k, v in self._score_dev(idxs, dmax).items()}
@@ -95,11 +110,14 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
         pairs it is given.
         alignment="dmax": the chen17 alignment instead, its score under 'dmax' in place of 'qmax'.
         That path may begin on the intermediate cell of a (2, 1) or (1, 2) step, so i0 or j0 may be 1
-        (a Qmax path never begins before row and column 2)."""
+        (a Qmax path never begins before row and column 2).
+        With n_oti > 1 the alignment is that of the winning transposition (the Qmax winner, or the
+        dmax winner under alignment="dmax"), 'oti' the shift applied and the score the best of n_oti;
+        finding the winner costs one extra scoring pass over idxs (also in align_path and rqa)."""
         align = self._alignment(alignment)
         self.prepare()
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = self._bank.crp_locate(idxs, align=align, **self._crp_kw())
+        r = self._bank.crp_locate(idxs, align=align, **self._crp_kw(), **self._picks_kw(idxs, align))
         cells = r["seg"].cpu().numpy()
         qf, rf = segment_frames(cells, self.m, self.tau, self.downsample_fac, self._n_frames[idxs[:, 0]],
                                 self._n_frames[idxs[:, 1]])
@@ -121,7 +139,7 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
         align = self._alignment(alignment)
         self.prepare()
         idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
-        r = self._bank.crp_path(idxs, align=align, **self._crp_kw())
+        r = self._bank.crp_path(idxs, align=align, **self._crp_kw(), **self._picks_kw(idxs, align))
         pc = r["cells"].cpu().numpy()
         return {alignment: r[alignment].cpu().numpy(), "oti": r["oti"].cpu().numpy(), "cells": r["seg"].cpu().numpy(),
                 "path_off": r["path_off"].cpu().numpy(), "path_cells": pc,
@@ -129,8 +147,9 @@ class ChromaBackedAlgorithm(CoverAlgorithm):
 
     def _rqa_dev(self, idxs, lmin=2, smax=True, hist_cap=0, lines=True):
         self.prepare()
-        return self._bank.crp_rqa(np.asarray(idxs, np.int32).reshape(-1, 2), lmin=lmin, smax=smax, hist_cap=hist_cap,
-                                  lines=lines, **self._crp_kw())
+        idxs = np.asarray(idxs, np.int32).reshape(-1, 2)
+        return self._bank.crp_rqa(idxs, lmin=lmin, smax=smax, hist_cap=hist_cap, lines=lines, **self._crp_kw(),
+                                  **self._picks_kw(idxs))
 
     def rqa(self, idxs, lmin=2, hist=False):
         """Cross-recurrence quantification of every (query, reference) pair of idxs (the definition:
@@ -162,28 +181,34 @@ class Serra09(ChromaBackedAlgorithm):
     MEASURES = MAXIMA + ("det", "lmean", "entr", "rr")
 
     @classmethod
-    def algorithm_name(cls, measure="qmax", binarize="percentile", oti_rank=1):
+    def algorithm_name(cls, measure="qmax", binarize="percentile", oti_rank=1, n_oti=1):
         """The name under which a Serra09 that scores by `measure` keeps its Ds cache and writes its
         results: 'Serra09' for Qmax (the reference's), 'Serra09-<measure>' for any other. On the
         OTI-binary CRP (binarize='oti') 'Serra09-otib', 'Serra09-otib<rank>' above rank 1, comes before
-        the measure: 'Serra09-otib2-det'."""
+        the measure: 'Serra09-otib2-det'. Best of n_oti > 1 transpositions adds '-oti<n>' after it:
+        'Serra09-oti2', 'Serra09-otib2-oti2-det'."""
         if measure not in cls.MEASURES:
             raise ValueError("measure must be one of %s, not %r" % (", ".join(cls.MEASURES), measure))
-        name = "Serra09" + _lib.binarize_suffix(binarize, oti_rank)
+        name = "Serra09" + _lib.binarize_suffix(binarize, oti_rank) + _lib.n_oti_suffix(n_oti)
         return name if measure == "qmax" else "%s-%s" % (name, measure)
 
     def __init__(self, dataset_csv, datapath, chroma_type='hpcp', shortname='benchmark', oti=True, kappa=0.095,
                  tau=1, m=9, downsample_fac=40, cachedir="cache", measure="qmax", lmin=2, binarize="percentile",
-                 oti_rank=1):
+                 oti_rank=1, n_oti=1):
         """binarize='oti': every CRP of this object (similarity, localize, align_path, rqa, measure=,
         the shortlist flow) is the OTI-binary CRP of Serra08 at oti_rank in 1 .. 12 (include/acoss_hip.h,
-        acoss_crp_params2) in place of the percentile CRP; kappa is then not read."""
-        name = self.algorithm_name(measure, binarize, oti_rank)
+        acoss_crp_params2) in place of the percentile CRP; kappa is then not read.
+        n_oti in 1 .. 12 (needs oti): Qmax is the best over the n_oti most probable transpositions of
+        the ranked OTI (Serra, Serra and Andrzejak 2009; include/acoss_hip.h, acoss_crp_params3), at
+        about n_oti times the scoring cost. localize, align_path, rqa and every measure other than
+        'qmax' run on the transposition that won Qmax (alignment="dmax": that won dmax), which they
+        first find with one extra scoring pass over their pairs."""
+        name = self.algorithm_name(measure, binarize, oti_rank, _lib.check_n_oti(n_oti, oti))
         if int(lmin) != lmin or lmin < 1:
             raise ValueError("lmin must be an integer >= 1, not %r" % (lmin,))
         self.measure = measure
         self.lmin = int(lmin)
-        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac, binarize, oti_rank)
+        self._init_chroma(chroma_type, oti, kappa, tau, m, downsample_fac, binarize, oti_rank, n_oti)
         CoverAlgorithm.__init__(self, dataset_csv=dataset_csv, name=name, datapath=datapath, shortname=shortname,
                                 cachedir=cachedir)
 

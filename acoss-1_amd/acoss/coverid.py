@@ -21,13 +21,13 @@ _LOG_FILE_PATH = "acoss.coverid.log"
 
 algorithm_names = ["Serra09", "EarlyFusionTraile", "LateFusionChen", "FTM2D", "SiMPle"]
 shortlist_algorithms = ("Serra09", "SiMPle")  # the alignment scorers that take an FTM2D shortlist
-binarize_algorithms = ("Serra09", "LateFusionChen")  # the scorers on a CRP, which take its binarisation
+binarize_algorithms = ("Serra09", "LateFusionChen")  # the scorers on a CRP, which take its binarisation and n_oti
 mutual_algorithms = ("EarlyFusionTraile", "EarlyFusion")  # the mutual nearest-neighbour binarisation
 
 
 def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09", shortname="covers80",
               parallel=True, n_workers=-1, cachedir="cache", shortlist=None, measure="qmax", binarize="percentile",
-              oti_rank=1, mutual=False):
+              oti_rank=1, mutual=False, n_oti=1):
     """Run one cover-ID algorithm over a dataset CSV and print/write its evaluation statistics.
     Returns the algorithm object (its Ds hold the similarity matrices).
     shortlist: None, or k: Serra09 / SiMPle score only each song's k best FTM2D candidates (shingles
@@ -38,6 +38,9 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
     binarize, oti_rank: Serra09 / LateFusionChen on the OTI-binary CRP of Serra08 (binarize='oti', oti_rank in
     1 .. 12; include/acoss_hip.h, acoss_crp_params2) in place of the percentile CRP; they run, cache and report
     as 'Serra09-otib', 'LateFusionChen-otib', with the rank appended above 1.
+    n_oti: Serra09 / LateFusionChen keep the best score over the n_oti (1 .. 12) most probable transpositions of the
+    ranked OTI (include/acoss_hip.h, acoss_crp_params3); above 1 they run, cache and report with '-oti<n>' appended:
+    'Serra09-oti2'.
     mutual: EarlyFusionTraile binarises by mutual nearest neighbours (Tralie 2017; include/acoss_hip.h,
     "mutual") in place of the reference's row rule; it runs, caches and reports as 'EarlyFusionTraile-mutual'."""
     logger = log(_LOG_FILE_PATH)
@@ -56,6 +59,10 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
     if (binarize != "percentile" or oti_rank != 1) and algorithm not in binarize_algorithms:
         raise ValueError("binarize and oti_rank are supported by %s only, not by '%s'"
                          % (" and ".join(binarize_algorithms), algorithm))
+    from ._lib import check_n_oti
+    n_oti = check_n_oti(n_oti)
+    if n_oti != 1 and algorithm not in binarize_algorithms:
+        raise ValueError("n_oti is supported by %s only, not by '%s'" % (" and ".join(binarize_algorithms), algorithm))
     from ._lib import check_ef_binarize
     if check_ef_binarize(mutual) and algorithm not in mutual_algorithms:
         raise ValueError("mutual is supported by EarlyFusionTraile only, not by '%s'" % algorithm)
@@ -75,7 +82,7 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         del first
     if algorithm == "Serra09":
         from .algorithms.rqa_serra09 import Serra09
-        algo = Serra09(measure=measure, binarize=binarize, oti_rank=oti_rank, **kw)
+        algo = Serra09(measure=measure, binarize=binarize, oti_rank=oti_rank, n_oti=n_oti, **kw)
         logger.info('Computing pairwise similarity...')
         algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True, candidates=candidates)
         algo.normalize_by_length()
@@ -91,7 +98,7 @@ def benchmark(dataset_csv, feature_dir, feature_type="hpcp", algorithm="Serra09"
         algo.do_late_fusion()
     elif algorithm == "LateFusionChen":
         from .algorithms.latefusion_chen import ChenFusion
-        algo = ChenFusion(binarize=binarize, oti_rank=oti_rank, **kw)
+        algo = ChenFusion(binarize=binarize, oti_rank=oti_rank, n_oti=n_oti, **kw)
         logger.info('Computing pairwise similarity...')
         algo.all_pairwise(parallel, n_cores=n_workers, symmetric=True)
         algo.normalize_by_length()
@@ -141,6 +148,9 @@ def parser_args(cmd_args):
     parser.add_argument('--oti-rank', type=int, action="store", default=1,
                         help="with --binarize oti: a cell is a hit when fewer than this many further "
                              "transpositions are closer (1 .. 12)")
+    parser.add_argument('--n-oti', type=int, action="store", default=1,
+                        help="Serra09 / LateFusionChen: keep the best score over this many of the most probable "
+                             "transpositions (1 .. 12)")
     parser.add_argument('--mutual', action="store_true",
                         help="EarlyFusionTraile: binarise by mutual nearest neighbours (rows and columns)")
     return parser.parse_args(cmd_args)
@@ -150,4 +160,5 @@ if __name__ == '__main__':
     args = parser_args(sys.argv[1:])
     benchmark(dataset_csv=args.dataset_csv, feature_dir=args.feature_dir, feature_type=args.chroma_type,
               algorithm=args.method, shortname=args.shortname, parallel=bool(args.parallel), n_workers=args.n_workers,
-              shortlist=args.shortlist, binarize=args.binarize, oti_rank=args.oti_rank, mutual=args.mutual)
+              shortlist=args.shortlist, binarize=args.binarize, oti_rank=args.oti_rank, mutual=args.mutual,
+              n_oti=args.n_oti)

@@ -135,36 +135,68 @@ class ChromaBank:
         """(key, shape, dtype name) of what crp_locate returns, for an empty pair list."""
         return ((_lib.score_key(align), 0, "float32"), ("seg", (0, 4), "int32"), ("oti", 0, "int32"))
 
+    def oti_ranked(self, pairs, dots=True):
+        """The ranked OTI of (query, reference) pairs: {"shifts" (P, 12), with dots "dots" (P, 12)}
+        device tensors (see _lib.oti_ranked): the twelve transpositions of the reference by descending
+        profile dot, shifts[:, 0] the OTI every CRP applies."""
+        torch = _lib._torch()
+        if (np.asarray(pairs).size if not isinstance(pairs, torch.Tensor) else pairs.numel()) == 0:
+            out = {"shifts": torch.zeros((0, 12), dtype=torch.int32, device="cuda")}
+            if dots:
+                out["dots"] = torch.zeros((0, 12), dtype=torch.float32, device="cuda")
+            return out
+        return _lib.oti_ranked(self.feats, self.off, self.len, pairs, dots=dots)
+
     def crp_align(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, qmax=True,
-                  dmax=False, want_oti=False, binarize="percentile", oti_rank=1):
+                  dmax=False, want_oti=False, binarize="percentile", oti_rank=1, n_oti=1):
         """Serra09 (Qmax) / Chen (dmax) scores for (query, reference) pairs. binarize='oti': on the
         OTI-binary CRP of Serra08 at oti_rank (include/acoss_hip.h, acoss_crp_params2; kappa is then
-        not read) in place of the percentile CRP; the same two arguments on the three methods below."""
+        not read) in place of the percentile CRP; the same two arguments on the three methods below.
+        n_oti > 1: the best score over the n_oti best transpositions of the ranked OTI
+        (acoss_crp_params3), each aligner with its own winner: "oti" and "pick_q" come with Qmax,
+        "oti_d" and "pick_d" with dmax (see _lib.crp_align)."""
+        n_oti = _lib.check_n_oti(n_oti, oti)
         empty = [(k, 0, dt) for k, dt, on in (("qmax", "float32", qmax), ("dmax", "float32", dmax),
                                               ("oti", "int32", want_oti)) if on]
+        if n_oti == 1:
+            return self._crp(_lib.crp_align, empty, pairs,
+                             (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank), qmax=qmax, dmax=dmax,
+                             oti=want_oti)
+        if qmax or want_oti:
+            empty += [("oti", 0, "int32")] * (not want_oti) + [("pick_q", 0, "int32")]
+        if dmax:
+            empty += [("oti_d", 0, "int32"), ("pick_d", 0, "int32")]
         return self._crp(_lib.crp_align, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank),
-                         qmax=qmax, dmax=dmax, oti=want_oti)
+                         qmax=qmax, dmax=dmax, oti=want_oti, n_oti=n_oti)
+
+    @staticmethod
+    def _picks(picks):
+        """The picks= of the three methods below as _lib takes it: nothing when None."""
+        return {} if picks is None else {"picks": picks}
 
     def crp_locate(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0,
-                   binarize="percentile", oti_rank=1):
+                   binarize="percentile", oti_rank=1, picks=None):
         """Qmax of (query, reference) pairs and where it lies: {"qmax", "seg" (P, 4), "oti"} device
         tensors (see _lib.crp_locate); the scores are crp_align's. align=1: dmax and the chen17
-        alignment, the score under "dmax"."""
+        alignment, the score under "dmax". picks ((P,) int32; also on the two methods below): the rank
+        of the ranked OTI each pair runs at, crp_align(n_oti=...)'s "pick_q" or "pick_d" for the
+        alignment that won; "oti" is the shift applied."""
         return self._crp(_lib.crp_locate, self._located(align), pairs,
-                         (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank), align=align)
+                         (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank), align=align,
+                         **self._picks(picks))
 
     def crp_path(self, pairs, m=9, tau=1, kappa=0.095, oti=True, gamma_open=0.5, gamma_ext=0.5, align=0,
-                 binarize="percentile", oti_rank=1):
+                 binarize="percentile", oti_rank=1, picks=None):
         """Qmax of (query, reference) pairs with the whole alignment path of each: {"qmax", "seg"
         (P, 4), "oti", "path_off" (P + 1,), "cells" (total, 2)} device tensors (see _lib.crp_path);
         scores and segments are crp_locate's. align=1: dmax and the chen17 path, the score under
         "dmax"; its steps also include (1, 0) and (0, 1) and i0 or j0 may be 1 (_lib.crp_path)."""
         empty = self._located(align) + (("path_off", 1, "int64"), ("cells", (0, 2), "int32"))
         return self._crp(_lib.crp_path, empty, pairs, (m, tau, kappa, oti, gamma_open, gamma_ext, binarize, oti_rank),
-                         align=align)
+                         align=align, **self._picks(picks))
 
     def crp_rqa(self, pairs, m=9, tau=1, kappa=0.095, oti=True, lmin=2, smax=True, hist_cap=0, lines=True,
-                binarize="percentile", oti_rank=1):
+                binarize="percentile", oti_rank=1, picks=None):
         """Cross-recurrence quantification of (query, reference) pairs: {"counts" (P, 4), "lmax",
         "stats" (P, 4), "oti"} device tensors, with smax "smax", with hist_cap > 0 "hist"
         (P, hist_cap) (see _lib.crp_rqa); the CRP is crp_align's. lines=False: "oti" and "smax" only."""
@@ -176,4 +208,4 @@ class ChromaBank:
         if hist_cap:
             empty.append(("hist", (0, int(hist_cap)), "int32"))
         return self._crp(_lib.crp_rqa, empty, pairs, (m, tau, kappa, oti, 0.5, 0.5, binarize, oti_rank), lmin=lmin,
-                         smax=smax, hist_cap=hist_cap, lines=lines)
+                         smax=smax, hist_cap=hist_cap, lines=lines, **self._picks(picks))

@@ -24,6 +24,10 @@
 //    CRP as one 32-bit word per (32-row strip, column): the layout the DP consumes.
 // Under ACOSS_BIN_OTI (the entries ending in 2) crp_masks runs a third producer of the same words,
 // crp_otib.hip's k_crp_otib, in place of both: no thresholds, no rolled reference, no key planes.
+// Under a ranked OTI (the entries ending in 3; the definition: include/acoss_hip.h, acoss_crp_params3)
+// k_oti_rank orders the twelve shifts of every pair of a DP batch, k_pair_oti applies the pair's pick of
+// that order in place of the argmax, and crp_batches runs crp_masks and the DP once per round of a best
+// of n, k_oti_fold keeping the best score with the shift and the pick that made it.
 // The wavefront DP over those words (k_crp_dp*, k_crp_dp_trace for acoss_crp_locate /
 // acoss_locate_crp, k_crp_dp_dir and k_crp_backtrack for acoss_crp_path / acoss_path_crp, each also
 // for chen17 under the _dmax entries) is crp_dp.hip; this file reaches it through launch_dp,
@@ -95,15 +99,91 @@ __global__ void k_track_pairs(const float* __restrict__ feats, const int64_t* __
     o[c] = make_float4(x[2 * c], nx ? x[12 + 2 * c] : 0.0f, x[2 * c + 1], nx ? x[12 + 2 * c + 1] : 0.0f);
 }
 
-// Per pair: OTI index (essentia optimalTranspositionIndex restated) and stacked dims.
+// The twelve profile dots of a pair, dot[k] for the reference rolled by k: the fmaf chain the OTI
+// compares (include/acoss_hip.h, acoss_crp_params3). Fully unrolled: dot[] stays in registers.
+__device__ __forceinline__ void profile_dots(const float* __restrict__ prof, int a, int b, float (&dot)[12]) {
+  float pq[12], pr[12];
+#pragma unroll
+  for (int c = 0; c < 12; ++c) {
+    pq[c] = prof[a * 12 + c];
+    pr[c] = prof[b * 12 + c];
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 12; ++c) acc = __builtin_fmaf(pq[c], pr[(c - k + 12) % 12], acc);
+    dot[k] = acc;
+  }
+}
+
+// Ranked OTI, one lane per pair: order[p][r] = the shift of rank r, by twelve fully unrolled
+// selections of the first strict maximum among the shifts not yet taken (a taken-bit per shift, so
+// no register array is indexed at run time and the result is a permutation whatever the dots
+// hold). Round 0 makes k_pair_oti's comparisons. dots (may be NULL): dot[p][k].
+__global__ void k_oti_rank(const float* __restrict__ prof, const int32_t* __restrict__ pairs, int64_t n_pairs,
+                           int32_t* __restrict__ order, float* __restrict__ dots) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  float dot[12];
+  profile_dots(prof, pairs[2 * p], pairs[2 * p + 1], dot);
+  unsigned taken = 0u;
+#pragma unroll
+  for (int r = 0; r < 12; ++r) {
+    int best = -1;
+    float bestv = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      if (!((taken >> k) & 1u) && (best < 0 || dot[k] > bestv)) {
+        bestv = dot[k];
+        best = k;
+      }
+    }
+    taken |= 1u << best;
+    order[12 * p + r] = best;
+  }
+  if (dots) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dots[12 * p + k] = dot[k];
+  }
+}
+
+// Best-of fold of round r: where the round's score is strictly larger (or r is 0), it becomes the
+// pair's best, with the shift and the pick that made it. best is the batch's own row, so an output
+// that was not asked for may be NULL.
+__global__ void k_oti_fold(const float* __restrict__ row, const int32_t* __restrict__ oti, int r, int nb,
+                           float* __restrict__ best, float* __restrict__ score_out, int32_t* __restrict__ oti_out,
+                           int32_t* __restrict__ pick_out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nb) return;
+  const float v = row[p];
+  if (r == 0 || v > best[p]) {
+    best[p] = v;
+    if (score_out) score_out[p] = v;
+    if (oti_out) oti_out[p] = oti[p];
+    if (pick_out) pick_out[p] = r;
+  }
+}
+
+// Per pair: OTI index (essentia optimalTranspositionIndex restated) and stacked dims. With an order
+// (k_oti_rank's, 12 per pair) the index is order[pick], pick the pair's entry of the picks plane or,
+// without a plane, the scalar; a pick outside 0 .. 11 raises *err and runs as pick 0.
 __global__ void k_pair_oti(const float* __restrict__ prof, const int32_t* __restrict__ len,
                            const int32_t* __restrict__ pairs, int64_t n_pairs, int use_oti, int m, int tau,
-                           int32_t* __restrict__ oti, int2* __restrict__ dims) {
+                           const int32_t* __restrict__ order, int pick, const int32_t* __restrict__ picks,
+                           int* __restrict__ err, int32_t* __restrict__ oti, int2* __restrict__ dims) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_pairs) return;
   const int a = pairs[2 * p], b = pairs[2 * p + 1];
   int best = 0;
-  if (use_oti) {
+  if (order) {
+    int r = picks ? picks[p] : pick;
+    if (r < 0 || r > 11) {
+      atomicOr(err, 1);
+      r = 0;
+    }
+    best = order[12 * p + r];
+  } else if (use_oti) {
     float pq[12], pr[12];
 #pragma unroll
     for (int c = 0; c < 12; ++c) {
@@ -500,6 +580,8 @@ enum CrpSlot {
   // the line walk's band-boundary records, likewise: acoss_crp_rqa; acoss_rqa_crp after its MatrixView,
   // followed by the Smax DP's
   SLOT_RQA = 29, SLOT_RQA_CRP = 30,
+  // ranked OTI (OtiWs): the pick flag, the orders of a DP batch and the best-of rows; acoss_oti_ranked: the profiles
+  SLOT_OTI = 32,
 };
 
 // Every driver below takes the wide params; the entries without a 2 widen theirs (binarize = 0).
@@ -531,6 +613,85 @@ int check_params(const acoss_crp_params2* P2) {
     set_error("oti_rank %d outside 1 .. 12", P2->oti_rank);
     return ACOSS_E_ARG;
   }
+  return ACOSS_OK;
+}
+
+// Which transposition of the ranked OTI a call applies (include/acoss_hip.h, acoss_crp_params3): best of
+// n_oti (acoss_crp_align3), else the scalar pick or the plane picks. The entries without a 3 pass {1, 0, NULL}.
+struct OtiSel {
+  int n_oti, pick;
+  const int32_t* picks;  // device, one per pair of the call; NULL: pick for every pair
+  bool ranked() const { return n_oti > 1 || pick != 0 || picks; }
+};
+
+const OtiSel kOtiFirst{1, 0, nullptr};
+
+OtiSel oti_sel(const acoss_crp_params3* P3, const int32_t* picks) {
+  return P3 ? OtiSel{P3->n_oti, P3->oti_pick, picks} : kOtiFirst;
+}
+
+// best_of: acoss_crp_align3, the one entry that reads n_oti and takes no pick.
+int check_oti(const acoss_crp_params2* P2, const OtiSel& S, bool best_of) {
+  if (S.n_oti < 1 || S.n_oti > 12) {
+    set_error("n_oti %d outside 1 .. 12", S.n_oti);
+    return ACOSS_E_ARG;
+  }
+  if (S.pick < 0 || S.pick > 11) {
+    set_error("oti_pick %d outside 0 .. 11", S.pick);
+    return ACOSS_E_ARG;
+  }
+  if (!best_of && S.n_oti != 1) {
+    set_error("n_oti %d: only acoss_crp_align3 folds several transpositions, this entry requires 1", S.n_oti);
+    return ACOSS_E_ARG;
+  }
+  if (best_of && S.pick != 0) {
+    set_error("oti_pick %d: acoss_crp_align3 runs picks 0 .. n_oti - 1 and requires 0", S.pick);
+    return ACOSS_E_ARG;
+  }
+  if (!P2->base.oti && S.ranked()) {
+    set_error("oti = 0 has no ranking: n_oti > 1, a nonzero oti_pick and a pick plane need oti = 1");
+    return ACOSS_E_ARG;
+  }
+  return ACOSS_OK;
+}
+
+// The ranked-OTI tables of one DP batch, in workspace slot SLOT_OTI.
+struct OtiWs {
+  int* err;          // raised by k_pair_oti at a pick outside 0 .. 11
+  int32_t* order;    // k_oti_rank's, 12 per pair; NULL: no ranking, k_pair_oti makes the argmax itself
+  float* row[2];     // best of n: the scores of the current round, by launch_dp's align
+  float* best[2];    // and the best so far
+};
+
+int oti_ws(int64_t nb, hipStream_t s, OtiWs& W) {
+  const size_t ob = align_up(48 * (size_t)nb, 256), rb = align_up(4 * (size_t)nb, 256);
+  char* ws = static_cast<char*>(workspace(SLOT_OTI, 256 + ob + 4 * rb));
+  if (!ws) return ACOSS_E_HIP;
+  W.err = reinterpret_cast<int*>(ws);
+  W.order = reinterpret_cast<int32_t*>(ws + 256);
+  for (int q = 0; q < 2; ++q) {
+    W.row[q] = reinterpret_cast<float*>(ws + 256 + ob + q * rb);
+    W.best[q] = reinterpret_cast<float*>(ws + 256 + ob + (2 + q) * rb);
+  }
+  ACOSS_HIP_CHECK(hipMemsetAsync(W.err, 0, 4, s));
+  return ACOSS_OK;
+}
+
+// After the launches of a call with a pick plane: waits for them and refuses a plane k_pair_oti flagged.
+int oti_finish(const OtiWs& W, hipStream_t s) {
+  int h_err = 0;
+  ACOSS_HIP_CHECK(hipMemcpyAsync(&h_err, W.err, 4, hipMemcpyDeviceToHost, s));
+  ACOSS_HIP_CHECK(hipStreamSynchronize(s));
+  if (h_err) {
+    set_error("picks holds a value outside 0 .. 11");
+    return ACOSS_E_ARG;
+  }
+  return ACOSS_OK;
+}
+
+int launch_oti_rank(const float* prof, const int32_t* pairs, int64_t n, int32_t* order, float* dots, hipStream_t s) {
+  hipLaunchKernelGGL(k_oti_rank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, prof, pairs, n, order, dots);
+  ACOSS_LAUNCH_CHECK();
   return ACOSS_OK;
 }
 
@@ -722,14 +883,15 @@ CrpBatch batch_view(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int
 // One DP batch (nb <= C.nb_alloc pairs at pb) up to its CRP: OTI, rolled references, row and
 // column thresholds (thr_*, T_*) and the mask words, on stream s. The one place that chooses
 // between the split path, the generic kernels and, under ACOSS_BIN_OTI, the OTI-binary kernel, which
-// needs neither the rolled references nor thresholds (thr_*, T_* are then not written).
+// needs neither the rolled references nor thresholds (thr_*, T_* are then not written). With W.order
+// the OTI is the pairs' pick of it: the scalar, or picks (already offset to the batch) where given.
 int crp_masks(const CrpPlan& C, const TrackPrep& T, const int32_t* pb, int nb, const acoss_crp_params2* params2,
-              hipStream_t s) {
+              const OtiWs& W, int pick, const int32_t* picks, hipStream_t s) {
   int rc;
   const acoss_crp_params* params = &params2->base;
   prof_begin(PH_OTI, s);
   hipLaunchKernelGGL(k_pair_oti, dim3((nb + 255) / 256), dim3(256), 0, s, T.prof, T.len, pb, (int64_t)nb, params->oti,
-                     C.m, C.tau, C.oti, C.dims);
+                     C.m, C.tau, W.order, pick, picks, W.err, C.oti, C.dims);
   ACOSS_LAUNCH_CHECK();
   if (otib(params2)) {
     prof_end(PH_OTI, s);
@@ -808,13 +970,18 @@ const auto no_hook = [](auto&&...) { return ACOSS_OK; };
 //                    is answered first) and before anything is allocated;
 //   setup(C, nbd)    once the plan is known: the entry sizes and fetches its own workspace slot
 //                    and may lower the DP batch nbd below C.nb_alloc;
-//   dp(C, base, nb)  launches the entry's DP for pairs [base, base + nb) under its own phases.
+//   dp(C, base, nb, r, W)  launches the entry's DP for pairs [base, base + nb) under its own phases;
+//                    r is the round of a best of n (0 elsewhere), W the batch's ranked-OTI tables.
+// Under a ranked OTI (sel.ranked()) a batch first makes its orders, then runs crp_masks and dp once
+// per round r < sel.n_oti at pick r (at the entry's pick when n_oti is 1). best_of: the entry is
+// acoss_crp_align3, which alone may ask for n_oti > 1.
 template <class Check, class Setup, class Dp>
 int crp_batches(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
                 int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2,
-                hipStream_t s, int32_t* oti_out, Check check, Setup setup, Dp dp) {
+                const OtiSel& sel, bool best_of, hipStream_t s, int32_t* oti_out, Check check, Setup setup, Dp dp) {
   int rc = check_params(params2);
   if (rc) return rc;
+  if ((rc = check_oti(params2, sel, best_of))) return rc;
   const acoss_crp_params* params = &params2->base;
   if (n_pairs < 0 || n_tracks < 0 || max_len < 0) {
     set_error("negative size");
@@ -834,13 +1001,24 @@ int crp_batches(const float* feats, const int64_t* track_off, const int32_t* tra
   prof_end(PH_PREP, s);
   int64_t nbd = C.nb_alloc;
   if ((rc = setup(C, nbd))) return rc;
+  OtiWs W{};
+  if (sel.ranked() && (rc = oti_ws(nbd, s, W))) return rc;
   for (int64_t base = 0; base < n_pairs; base += nbd) {
     const int nb = (int)((n_pairs - base) < nbd ? (n_pairs - base) : nbd);
-    if ((rc = crp_masks(C, T, pairs + 2 * base, nb, params2, s))) return rc;
-    if ((rc = dp(C, base, nb))) return rc;
+    const int32_t* pb = pairs + 2 * base;
+    if (W.order) {
+      prof_begin(PH_OTI, s);
+      if ((rc = launch_oti_rank(T.prof, pb, nb, W.order, nullptr, s))) return rc;
+      prof_end(PH_OTI, s);
+    }
+    for (int r = 0; r < sel.n_oti; ++r) {
+      if ((rc = crp_masks(C, T, pb, nb, params2, W, best_of ? r : sel.pick, sel.picks ? sel.picks + base : nullptr, s)))
+        return rc;
+      if ((rc = dp(C, base, nb, r, W))) return rc;
+    }
     if (oti_out) ACOSS_HIP_CHECK(hipMemcpyAsync(oti_out + base, C.oti, 4 * nb, hipMemcpyDeviceToDevice, s));
   }
-  return ACOSS_OK;
+  return sel.picks ? oti_finish(W, s) : ACOSS_OK;
 }
 
 // The direction plane of one DP batch stays under this many bytes (acoss_crp_path shrinks its DP
@@ -948,8 +1126,8 @@ int crp_align_any(const float* feats, const int64_t* track_off, const int32_t* t
   float* const out[2] = {qmax_out, dmax_out};  // by launch_dp's align: 0 = Qmax, 1 = dmax
   const int phase[2] = {PH_DP_QMAX, PH_DP_DMAX};
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out, no_hook, no_hook,
-      [&](const CrpPlan& C, int64_t base, int nb) {
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, kOtiFirst, false, s, oti_out, no_hook,
+      no_hook, [&](const CrpPlan& C, int64_t base, int nb, int, const OtiWs&) {
         for (int align = 0; align < 2; ++align) {
           if (!out[align]) continue;
           prof_begin(phase[align], s);
@@ -962,11 +1140,39 @@ int crp_align_any(const float* feats, const int64_t* track_off, const int32_t* t
       });
 }
 
-int crp_pair_any(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params2* params2, float* dist,
-                 float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti, uint8_t* closer_out, void* hip_stream) {
+// acoss_crp_align3 at n_oti > 1: per round the DPs write the batch's scratch rows and k_oti_fold
+// keeps the best; by launch_dp's align, out / oti / pick = {Qmax's, dmax's}.
+int crp_align_best(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                   int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params3,
+                   float* const (&out)[2], int32_t* const (&oti)[2], int32_t* const (&pick)[2], hipStream_t s) {
+  const acoss_crp_params* params = &params3->base.base;
+  const int phase[2] = {PH_DP_QMAX, PH_DP_DMAX};
+  return crp_batches(
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, &params3->base, oti_sel(params3, nullptr), true,
+      s, nullptr, no_hook, no_hook, [&](const CrpPlan& C, int64_t base, int nb, int r, const OtiWs& W) {
+        for (int align = 0; align < 2; ++align) {
+          if (!out[align] && !oti[align] && !pick[align]) continue;
+          prof_begin(phase[align], s);
+          launch_dp(align, params->gamma_open == params->gamma_ext, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims,
+                    params->gamma_open, params->gamma_ext, C.bnd, C.bnd_stride, W.row[align], s);
+          ACOSS_LAUNCH_CHECK();
+          hipLaunchKernelGGL(k_oti_fold, dim3((nb + 255) / 256), dim3(256), 0, s, W.row[align], C.oti, r, nb,
+                             W.best[align], out[align] ? out[align] + base : nullptr,
+                             oti[align] ? oti[align] + base : nullptr, pick[align] ? pick[align] + base : nullptr);
+          ACOSS_LAUNCH_CHECK();
+          prof_end(phase[align], s);
+        }
+        return ACOSS_OK;
+      });
+}
+
+int crp_pair_any(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params2* params2,
+                 const OtiSel& sel, float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti,
+                 uint8_t* closer_out, void* hip_stream) {
   clear_error();
   int rc = check_params(params2);
   if (rc) return rc;
+  if ((rc = check_oti(params2, sel, false))) return rc;
   const acoss_crp_params* params = &params2->base;
   if (otib(params2) && (thr_row || thr_col)) {
     set_error("thr_row and thr_col must be NULL under ACOSS_BIN_OTI: it has no thresholds");
@@ -1005,7 +1211,12 @@ int crp_pair_any(const float* X, int32_t M, const float* Y, int32_t N, const aco
   ACOSS_HIP_CHECK(hipMemcpy(d_pairs, h_pairs, sizeof(h_pairs), hipMemcpyHostToDevice));
   TrackPrep T;
   if ((rc = run_prep(f, d_off, d_len, 2, max_len, m, tau, s, &T))) return rc;
-  if ((rc = crp_masks(C, T, d_pairs, 1, params2, s))) return rc;
+  OtiWs W{};
+  if (sel.ranked()) {
+    if ((rc = oti_ws(1, s, W))) return rc;
+    if ((rc = launch_oti_rank(T.prof, d_pairs, 1, W.order, nullptr, s))) return rc;
+  }
+  if ((rc = crp_masks(C, T, d_pairs, 1, params2, W, sel.pick, nullptr, s))) return rc;
   if (dist) {  // the roll is the pair's OTI, read from the track itself: under ACOSS_BIN_OTI this is D_0
     hipLaunchKernelGGL(k_crp_panel<1>, dim3((Np + kPanelW - 1) / kPanelW, C.nstrips, 1), dim3(256), C.pan_lds, s,
                        batch_view(C, T, d_pairs, 0), C.T_r, C.T_c, C.thr_stride, C.mask, C.mask_stride, C.ld, dist);
@@ -1049,13 +1260,66 @@ extern "C" int acoss_crp_pair(const float* X, int32_t M, const float* Y, int32_t
                               float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti,
                               void* hip_stream) {
   acoss_crp_params2 W;
-  return crp_pair_any(X, M, Y, N, widen(params, W), dist, thr_row, thr_col, crp, oti, nullptr, hip_stream);
+  return crp_pair_any(X, M, Y, N, widen(params, W), kOtiFirst, dist, thr_row, thr_col, crp, oti, nullptr, hip_stream);
 }
 
 extern "C" int acoss_crp_pair2(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params2* params,
                                float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti,
                                uint8_t* closer_out, void* hip_stream) {
-  return crp_pair_any(X, M, Y, N, params, dist, thr_row, thr_col, crp, oti, closer_out, hip_stream);
+  return crp_pair_any(X, M, Y, N, params, kOtiFirst, dist, thr_row, thr_col, crp, oti, closer_out, hip_stream);
+}
+
+extern "C" int acoss_crp_pair3(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params3* params,
+                               float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti,
+                               uint8_t* closer_out, void* hip_stream) {
+  return crp_pair_any(X, M, Y, N, params ? &params->base : nullptr, oti_sel(params, nullptr), dist, thr_row, thr_col,
+                      crp, oti, closer_out, hip_stream);
+}
+
+extern "C" int acoss_crp_align3(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                const acoss_crp_params3* params, float* qmax_out, float* dmax_out, int32_t* oti_q_out,
+                                int32_t* oti_d_out, int32_t* pick_q_out, int32_t* pick_d_out, void* hip_stream) {
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if (params && (params->n_oti != 1 || params->oti_pick != 0)) {
+    clear_error();
+    float* const out[2] = {qmax_out, dmax_out};
+    int32_t* const oti[2] = {oti_q_out, oti_d_out};
+    int32_t* const pick[2] = {pick_q_out, pick_d_out};
+    return crp_align_best(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, out, oti, pick, s);
+  }
+  // one transposition: acoss_crp_align2 itself, both winners its OTI at pick 0
+  const int rc = crp_align_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs,
+                               params ? &params->base : nullptr, qmax_out, dmax_out,
+                               oti_q_out ? oti_q_out : oti_d_out, hip_stream);
+  if (rc || n_pairs == 0) return rc;
+  if (oti_q_out && oti_d_out)
+    ACOSS_HIP_CHECK(hipMemcpyAsync(oti_d_out, oti_q_out, 4 * (size_t)n_pairs, hipMemcpyDeviceToDevice, s));
+  if (pick_q_out) ACOSS_HIP_CHECK(hipMemsetAsync(pick_q_out, 0, 4 * (size_t)n_pairs, s));
+  if (pick_d_out) ACOSS_HIP_CHECK(hipMemsetAsync(pick_d_out, 0, 4 * (size_t)n_pairs, s));
+  return ACOSS_OK;
+}
+
+extern "C" int acoss_oti_ranked(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                int32_t n_tracks, const int32_t* pairs, int64_t n_pairs, int32_t* shifts_out,
+                                float* dots_out, void* hip_stream) {
+  clear_error();
+  if (n_pairs < 0 || n_tracks < 0) {
+    set_error("negative size");
+    return ACOSS_E_ARG;
+  }
+  if (n_pairs == 0) return ACOSS_OK;
+  if (!feats || !track_off || !track_len || !pairs || !shifts_out || n_tracks == 0) {
+    set_error("NULL input pointer, no track or shifts_out is NULL");
+    return ACOSS_E_ARG;
+  }
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  float* prof = static_cast<float*>(workspace(SLOT_OTI, 12 * sizeof(float) * (size_t)n_tracks));
+  if (!prof) return ACOSS_E_HIP;
+  hipLaunchKernelGGL(k_track_profile, dim3((n_tracks + 3) / 4), dim3(64), 0, s, feats, track_off, track_len, n_tracks,
+                     prof);
+  ACOSS_LAUNCH_CHECK();
+  return launch_oti_rank(prof, pairs, n_pairs, shifts_out, dots_out, s);
 }
 
 extern "C" int acoss_align_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t align, float gamma_open,
@@ -1101,9 +1365,9 @@ int check_rqa_line(int longest) {
 }
 
 int crp_rqa_any(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
-                int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2, int32_t lmin,
-                int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out, int32_t* oti_out,
-                int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
+                int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2,
+                const OtiSel& sel, int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
   clear_error();
   const acoss_crp_params* params = params2 ? &params2->base : nullptr;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -1111,7 +1375,7 @@ int crp_rqa_any(const float* feats, const int64_t* track_off, const int32_t* tra
   void* rb = nullptr;  // band-boundary records of the line walk, rstride per pair
   int64_t rstride = 0;
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out,
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, sel, false, s, oti_out,
       [&] {
         if (int rc = check_rqa_args("acoss_crp_rqa", lmin, hist_cap, hist_out)) return rc;
         return lines ? check_rqa_line(stacked_len(max_len, params->m, params->tau)) : ACOSS_OK;
@@ -1121,7 +1385,7 @@ int crp_rqa_any(const float* feats, const int64_t* track_off, const int32_t* tra
         rb = workspace(SLOT_RQA, kRqaRecBytes * (size_t)rstride * (size_t)nbd);
         return rb ? ACOSS_OK : ACOSS_E_HIP;
       },
-      [&](const CrpPlan& C, int64_t base, int nb) {
+      [&](const CrpPlan& C, int64_t base, int nb, int, const OtiWs&) {
         if (lines) {
           prof_begin(PH_RQA, s);
           launch_rqa(nb, C.L, C.L + 1, C.mask, C.mask_stride, C.ld, C.dims, lmin, rb, rstride,
@@ -1149,16 +1413,26 @@ extern "C" int acoss_crp_rqa(const float* feats, const int64_t* track_off, const
                              int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
                              int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
   acoss_crp_params2 W;
-  return crp_rqa_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), lmin, counts_out,
-                     lmax_out, stats_out, smax_out, oti_out, hist_cap, hist_out, hip_stream);
+  return crp_rqa_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), kOtiFirst, lmin,
+                     counts_out, lmax_out, stats_out, smax_out, oti_out, hist_cap, hist_out, hip_stream);
 }
 
 extern "C" int acoss_crp_rqa2(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
                               int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params,
                               int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
                               int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream) {
-  return crp_rqa_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, lmin, counts_out,
-                     lmax_out, stats_out, smax_out, oti_out, hist_cap, hist_out, hip_stream);
+  return crp_rqa_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, kOtiFirst, lmin,
+                     counts_out, lmax_out, stats_out, smax_out, oti_out, hist_cap, hist_out, hip_stream);
+}
+
+extern "C" int acoss_crp_rqa3(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                              int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params,
+                              int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                              int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, const int32_t* picks,
+                              void* hip_stream) {
+  return crp_rqa_any(feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params ? &params->base : nullptr,
+                     oti_sel(params, picks), lmin, counts_out, lmax_out, stats_out, smax_out, oti_out, hist_cap,
+                     hist_out, hip_stream);
 }
 
 extern "C" int acoss_rqa_crp(const uint8_t* crp, int32_t M, int32_t N, int32_t lmin, int64_t* counts_out,
@@ -1216,15 +1490,15 @@ int path_bound(int align, int M, int N) { return align == 0 ? (M < N ? M : N) : 
 
 int crp_locate_any(int align, const float* feats, const int64_t* track_off, const int32_t* track_len,
                    int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
-                   const acoss_crp_params2* params2, float* score_out, int32_t* seg_out, int32_t* oti_out,
-                   void* hip_stream) {
+                   const acoss_crp_params2* params2, const OtiSel& sel, float* score_out, int32_t* seg_out,
+                   int32_t* oti_out, void* hip_stream) {
   clear_error();
   const acoss_crp_params* params = params2 ? &params2->base : nullptr;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   void* tb = nullptr;  // band-boundary records of the tracing DP, tstride per pair
   int64_t tstride = 0;
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out,
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, sel, false, s, oti_out,
       [&] {
         if (!seg_out) {
           set_error("seg_out is NULL");
@@ -1237,7 +1511,7 @@ int crp_locate_any(int align, const float* feats, const int64_t* track_off, cons
         tb = workspace(SLOT_LOCATE, kTraceRecBytes * (size_t)tstride * (size_t)nbd);
         return tb ? ACOSS_OK : ACOSS_E_HIP;
       },
-      [&](const CrpPlan& C, int64_t base, int nb) {
+      [&](const CrpPlan& C, int64_t base, int nb, int, const OtiWs&) {
         prof_begin(PH_DP_TRACE, s);
         launch_trace(align, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, tb,
                      tstride, score_out ? score_out + base : nullptr, seg_out + 4 * base, s);
@@ -1268,8 +1542,8 @@ int locate_crp_any(int align, const char* entry, const uint8_t* crp, int32_t M, 
 
 int crp_path_any(int align, const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
                  int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params2* params2,
-                 float* score_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
-                 int32_t* path_out, void* hip_stream) {
+                 const OtiSel& sel, float* score_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap,
+                 int32_t* len_out, int32_t* path_out, void* hip_stream) {
   clear_error();
   const acoss_crp_params* params = params2 ? &params2->base : nullptr;
   if (path_cap < 0) {
@@ -1282,7 +1556,7 @@ int crp_path_any(int align, const float* feats, const int64_t* track_off, const 
   uint32_t* endkey = nullptr;
   int64_t pstride = 0, bstride = 0;
   return crp_batches(
-      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, s, oti_out,
+      feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params2, sel, false, s, oti_out,
       [&] {
         if (!len_out || !path_out) {
           set_error("len_out or path_out is NULL");
@@ -1316,7 +1590,7 @@ int crp_path_any(int align, const float* feats, const int64_t* track_off, const 
         endkey = reinterpret_cast<uint32_t*>(ws + plane_bytes + bnd_bytes);
         return ACOSS_OK;
       },
-      [&](const CrpPlan& C, int64_t base, int nb) {
+      [&](const CrpPlan& C, int64_t base, int nb, int, const OtiWs&) {
         prof_begin(PH_DP_DIR, s);
         launch_dir(align, nb, C.L, C.mask, C.mask_stride, C.ld, C.dims, params->gamma_open, params->gamma_ext, bnd,
                    bstride, plane, pstride, endkey, score_out ? score_out + base : nullptr, s);
@@ -1374,16 +1648,25 @@ extern "C" int acoss_crp_locate(const float* feats, const int64_t* track_off, co
                                 const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                                 void* hip_stream) {
   acoss_crp_params2 W;
-  return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), qmax_out,
-                        seg_out, oti_out, hip_stream);
+  return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), kOtiFirst,
+                        qmax_out, seg_out, oti_out, hip_stream);
 }
 
 extern "C" int acoss_crp_locate2(const float* feats, const int64_t* track_off, const int32_t* track_len,
                                  int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
                                  const acoss_crp_params2* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                                  void* hip_stream) {
-  return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, qmax_out, seg_out,
-                        oti_out, hip_stream);
+  return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, kOtiFirst, qmax_out,
+                        seg_out, oti_out, hip_stream);
+}
+
+extern "C" int acoss_crp_locate3(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                 int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                 const acoss_crp_params3* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                                 const int32_t* picks, void* hip_stream) {
+  return crp_locate_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs,
+                        params ? &params->base : nullptr, oti_sel(params, picks), qmax_out, seg_out, oti_out,
+                        hip_stream);
 }
 
 extern "C" int acoss_crp_locate_dmax(const float* feats, const int64_t* track_off, const int32_t* track_len,
@@ -1391,16 +1674,25 @@ extern "C" int acoss_crp_locate_dmax(const float* feats, const int64_t* track_of
                                      const acoss_crp_params* params, float* dmax_out, int32_t* seg_out,
                                      int32_t* oti_out, void* hip_stream) {
   acoss_crp_params2 W;
-  return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), dmax_out,
-                        seg_out, oti_out, hip_stream);
+  return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), kOtiFirst,
+                        dmax_out, seg_out, oti_out, hip_stream);
 }
 
 extern "C" int acoss_crp_locate_dmax2(const float* feats, const int64_t* track_off, const int32_t* track_len,
                                       int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
                                       const acoss_crp_params2* params, float* dmax_out, int32_t* seg_out,
                                       int32_t* oti_out, void* hip_stream) {
-  return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, dmax_out, seg_out,
-                        oti_out, hip_stream);
+  return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, kOtiFirst, dmax_out,
+                        seg_out, oti_out, hip_stream);
+}
+
+extern "C" int acoss_crp_locate_dmax3(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                      int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                      const acoss_crp_params3* params, float* dmax_out, int32_t* seg_out,
+                                      int32_t* oti_out, const int32_t* picks, void* hip_stream) {
+  return crp_locate_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs,
+                        params ? &params->base : nullptr, oti_sel(params, picks), dmax_out, seg_out, oti_out,
+                        hip_stream);
 }
 
 extern "C" int acoss_locate_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,
@@ -1418,16 +1710,26 @@ extern "C" int acoss_crp_path(const float* feats, const int64_t* track_off, cons
                               const acoss_crp_params* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                               int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
   acoss_crp_params2 W;
-  return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), qmax_out,
-                      seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
+  return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), kOtiFirst,
+                      qmax_out, seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
 }
 
 extern "C" int acoss_crp_path2(const float* feats, const int64_t* track_off, const int32_t* track_len,
                                int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
                                const acoss_crp_params2* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
                                int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
-  return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, qmax_out, seg_out,
-                      oti_out, path_cap, len_out, path_out, hip_stream);
+  return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, kOtiFirst, qmax_out,
+                      seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
+}
+
+extern "C" int acoss_crp_path3(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                               int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                               const acoss_crp_params3* params, float* qmax_out, int32_t* seg_out, int32_t* oti_out,
+                               int32_t path_cap, int32_t* len_out, int32_t* path_out, const int32_t* picks,
+                               void* hip_stream) {
+  return crp_path_any(0, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs,
+                      params ? &params->base : nullptr, oti_sel(params, picks), qmax_out, seg_out, oti_out, path_cap,
+                      len_out, path_out, hip_stream);
 }
 
 extern "C" int acoss_crp_path_dmax(const float* feats, const int64_t* track_off, const int32_t* track_len,
@@ -1435,8 +1737,8 @@ extern "C" int acoss_crp_path_dmax(const float* feats, const int64_t* track_off,
                                    const acoss_crp_params* params, float* dmax_out, int32_t* seg_out, int32_t* oti_out,
                                    int32_t path_cap, int32_t* len_out, int32_t* path_out, void* hip_stream) {
   acoss_crp_params2 W;
-  return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), dmax_out,
-                      seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
+  return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, widen(params, W), kOtiFirst,
+                      dmax_out, seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
 }
 
 extern "C" int acoss_crp_path_dmax2(const float* feats, const int64_t* track_off, const int32_t* track_len,
@@ -1444,8 +1746,18 @@ extern "C" int acoss_crp_path_dmax2(const float* feats, const int64_t* track_off
                                     const acoss_crp_params2* params, float* dmax_out, int32_t* seg_out,
                                     int32_t* oti_out, int32_t path_cap, int32_t* len_out, int32_t* path_out,
                                     void* hip_stream) {
-  return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, dmax_out, seg_out,
-                      oti_out, path_cap, len_out, path_out, hip_stream);
+  return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs, params, kOtiFirst, dmax_out,
+                      seg_out, oti_out, path_cap, len_out, path_out, hip_stream);
+}
+
+extern "C" int acoss_crp_path_dmax3(const float* feats, const int64_t* track_off, const int32_t* track_len,
+                                    int32_t n_tracks, int32_t max_len, const int32_t* pairs, int64_t n_pairs,
+                                    const acoss_crp_params3* params, float* dmax_out, int32_t* seg_out,
+                                    int32_t* oti_out, int32_t path_cap, int32_t* len_out, int32_t* path_out, const int32_t* picks,
+                                    void* hip_stream) {
+  return crp_path_any(1, feats, track_off, track_len, n_tracks, max_len, pairs, n_pairs,
+                      params ? &params->base : nullptr, oti_sel(params, picks), dmax_out, seg_out, oti_out, path_cap,
+                      len_out, path_out, hip_stream);
 }
 
 extern "C" int acoss_path_crp(const uint8_t* crp, int32_t M, int32_t N, float gamma_open, float gamma_ext,

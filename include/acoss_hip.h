@@ -307,6 +307,78 @@ int acoss_crp_rqa2(const float* feats, const int64_t* track_off, const int32_t* 
                    int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
                    int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, void* hip_stream);
 
+/* Ranked OTI: align over the n best transpositions, keep the best (Serra, Serra and Andrzejak 2009
+ * compute Qmax for the few most probable transpositions and keep the largest; essentia's oti=True
+ * and the entries above apply one index only).
+ *
+ * The definition, for a pair (query a, reference b) with mean-chroma profiles pq, pr (what
+ * k_track_profile writes, oracle.profile):
+ *   dot_k, k = 0 .. 11: the float32 chain acc = fmaf(pq[c], pr[(c - k + 12) % 12], acc) for
+ *     c = 0 .. 11 from acc = 0: the values the global OTI compares.
+ *   order: the twelve shifts sorted by dot_k descending, equal dots keeping the smaller shift first
+ *     (a stable sort), built as twelve selections of "the first strict maximum among the shifts not
+ *     yet taken". order[0] is the OTI of the entries above, by the same comparisons.
+ *   pick r (0 .. 11) applies order[r] wherever the OTI index is applied: the roll of the reference
+ *     under ACOSS_BIN_PERCENTILE, g under ACOSS_BIN_OTI. Nothing else changes: the distance is
+ *     oracle.crp_dist(X, Y, order[r], m, tau), norms of the un-rolled tracks.
+ *   best of n (n_oti = n in 1 .. 12): a score (Qmax, dmax) is the maximum over picks 0 .. n - 1,
+ *     folded in pick order with a strict >, so the smallest pick attaining it wins; Qmax and dmax
+ *     each keep their own winner.
+ * With oti = 0 there is no ranking: n_oti > 1, a nonzero oti_pick or a pick plane then return
+ * ACOSS_E_ARG, as do n_oti outside 1 .. 12 and oti_pick outside 0 .. 11. */
+typedef struct acoss_crp_params3 {
+  acoss_crp_params2 base;
+  int32_t n_oti;     /* 1 .. 12, read by acoss_crp_align3 only; the others require 1 */
+  int32_t oti_pick;  /* 0 .. 11, applied to every pair when no pick plane is given; acoss_crp_align3 requires 0 */
+} acoss_crp_params3;
+
+/* order and dot_k of every pair: shifts_out int32[n_pairs][12] = order, dots_out float[n_pairs][12]
+ * = dot_k indexed by the shift k (may be NULL). Device pointers; runs the profile kernel of the
+ * aligners and one lane per pair. */
+int acoss_oti_ranked(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                     const int32_t* pairs, int64_t n_pairs, int32_t* shifts_out, float* dots_out, void* hip_stream);
+
+/* acoss_crp_align2 with best of n_oti. qmax_out / dmax_out: the best-of-n scores; oti_q_out,
+ * oti_d_out: the shifts that won them; pick_q_out, pick_d_out: the winning picks (int32[n_pairs]
+ * each). Every output may be NULL; an aligner none of whose three outputs is asked for does not
+ * run. Per DP batch (ACOSS_BATCH_PAIRS chunking as before) the order is made once, then each round
+ * r < n_oti runs the CRP at pick r, the DPs into a scratch row and a fold into the outputs; the
+ * per-track preparation runs once per call. n_oti = 1 makes no order and is acoss_crp_align2 bit
+ * for bit (picks 0, both shifts its oti_out). */
+int acoss_crp_align3(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                     int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params,
+                     float* qmax_out, float* dmax_out, int32_t* oti_q_out, int32_t* oti_d_out, int32_t* pick_q_out,
+                     int32_t* pick_d_out, void* hip_stream);
+/* acoss_crp_pair2 at the scalar pick params->oti_pick: dist, thr_row, thr_col, crp, closer_out and
+ * oti are those of the transposition order[oti_pick]. n_oti must be 1. */
+int acoss_crp_pair3(const float* X, int32_t M, const float* Y, int32_t N, const acoss_crp_params3* params,
+                    float* dist, float* thr_row, float* thr_col, uint8_t* crp, int32_t* oti, uint8_t* closer_out,
+                    void* hip_stream);
+/* The entries ending in 2 with one more argument: picks, device int32[n_pairs], the pick of every
+ * pair; NULL means params->oti_pick for every pair. oti_out is the shift applied. n_oti must be 1.
+ * A pick outside 0 .. 11 in the plane returns ACOSS_E_ARG after the call has run (a device flag read
+ * back; that pair ran at pick 0): these entries then synchronise the stream once. With oti_pick = 0
+ * and picks = NULL each is its twin ending in 2, bit for bit. */
+int acoss_crp_locate3(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                      int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params,
+                      float* qmax_out, int32_t* seg_out, int32_t* oti_out, const int32_t* picks, void* hip_stream);
+int acoss_crp_locate_dmax3(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                           int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params,
+                           float* dmax_out, int32_t* seg_out, int32_t* oti_out, const int32_t* picks,
+                           void* hip_stream);
+int acoss_crp_path3(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                    int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params,
+                    float* qmax_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
+                    int32_t* path_out, const int32_t* picks, void* hip_stream);
+int acoss_crp_path_dmax3(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                         int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params,
+                         float* dmax_out, int32_t* seg_out, int32_t* oti_out, int32_t path_cap, int32_t* len_out,
+                         int32_t* path_out, const int32_t* picks, void* hip_stream);
+int acoss_crp_rqa3(const float* feats, const int64_t* track_off, const int32_t* track_len, int32_t n_tracks,
+                   int32_t max_len, const int32_t* pairs, int64_t n_pairs, const acoss_crp_params3* params,
+                   int32_t lmin, int64_t* counts_out, int32_t* lmax_out, double* stats_out, float* smax_out,
+                   int32_t* oti_out, int32_t hist_cap, int32_t* hist_out, const int32_t* picks, void* hip_stream);
+
 /* acoss smith_waterman_constrained (A8, acoss/algorithms/utils/alignment_tools.py:25-46) on
  * a batch of binary matrices: matrix b is (rows[b] x cols[b]) uint8 at byte offset off[b]
  * of `mats`. score_out: double[n_mats]. Bit-exact float64 (same evaluation order). */
