@@ -2,7 +2,7 @@
 
 `smith_waterman_constrained` keeps the reference's signature (one binary matrix -> float);
 `smith_waterman_constrained_batch` scores a list of matrices in one launch (one wavefront
-per matrix, misc.hip k_sw). Non-binary input raises IOError like `match` (:17-23).
+per matrix, sw.hip k_swb). Non-binary input raises IOError like `match` (:17-23).
 """
 import numpy as np
 

@@ -115,7 +115,7 @@ __device__ inline double wave_max(double v) {
 // Value of lane `src` (wave-uniform) in every lane: v_readlane, no LDS.
 __device__ __forceinline__ int lane_bcast(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 
-// The n cells a backtrack (crp_dp.hip, sw_path.hip) left in out[], last to first, turned round by
+// The n cells a backtrack (crp_dp.hip, sw.hip) left in out[], last to first, turned round by
 // the whole wave, and -1 after them up to path_cap.
 __device__ __forceinline__ void path_turn_and_pad(int2* out, int n, int path_cap, int lane) {
   for (int t = lane; t < n / 2; t += 64) {

@@ -21,8 +21,8 @@
 //                 LDS tiles) and column (k_ef_kmin, a thread per column), K <= 16; k_ef_kmean, a
 //                 wave-per-line select, beyond that
 //   k_ef_wsum     elementwise: E = exp(-(((0 + W_m) + W_s) + W_c)) in float32, exp = canon_expf
-//   SW            ef_launch_swmeta, then launch_swb_batch (misc.hip) over the 4P bit planes; for the
-//                 locate and path entries launch_swt_locate / launch_swt_path (sw_path.hip) instead
+//   SW            ef_launch_swmeta, then launch_swb_batch (sw.hip) over the 4P bit planes; for the
+//                 locate and path entries launch_swt_locate / launch_swt_path (sw.hip) instead
 // Tolerance vs the reference: the GEMMs' summation order (BLAS vs MFMA), the k-smallest means'
 // order (ascending here, np.partition's unspecified there) and exp (canon_expf vs numpy's); every
 // other step is the reference's float32 arithmetic. Against the canonical CPU oracle

@@ -1,17 +1,17 @@
-// sw_internal.hpp — the constrained Smith-Waterman walk over bit planes, as misc.hip (the byte
-// matrices of acoss_sw_*), earlyfusion.hip (the four matrices of a pair) and sw_path.hip share it.
+// sw_internal.hpp — the constrained Smith-Waterman walk over bit planes (sw.hip), as earlyfusion.hip
+// and ef_snf.hip (the four matrices of a pair) launch it.
 #pragma once
 #include "common.hpp"
 
 namespace acoss {
 
-// Scores (misc.hip): matrix mid's words start at W + mid * wstride, row stride ldw words (word
+// Scores: matrix mid's words start at W + mid * wstride, row stride ldw words (word
 // [g][c] holds rows 16 g .. 16 g + 15 of column c); bnd: sw_bnd_bytes per matrix.
 size_t sw_bnd_bytes(int max_rows, int max_cols);
 int launch_swb_batch(const uint16_t* W, int64_t wstride, int ldw, const int32_t* rows, const int32_t* cols, int n,
                      int max_rows, int max_cols, void* bnd, double* out, hipStream_t s);
 
-// Where the alignment lies (sw_path.hip; the definition: include/acoss_hip.h, acoss_sw_locate), over
+// Where the alignment lies (the definition: include/acoss_hip.h, acoss_sw_locate), over
 // the same planes, for matrices of at most kSwCellMax rows and columns. Both DPs keep 8 rows per
 // lane at every shape. bnd: swt_bnd_bytes per matrix, read and written only by matrices of more
 // than 512 rows. score may be NULL.

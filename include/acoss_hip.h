@@ -390,7 +390,7 @@ int acoss_sw_constrained(const uint8_t* mats, const int64_t* off, const int32_t*
  * (acoss_sw_path). The reference fills a whole score matrix and returns only its maximum; here the
  * tracing DP carries the cell where each path began beside every score and writes no matrix, and
  * the direction DP leaves a 2-bit predecessor code per cell in a workspace plane of about M N / 4
- * bytes per matrix that a second kernel walks back (sw_path.hip k_swt, k_sw_backtrack). Inputs as
+ * bytes per matrix that a second kernel walks back (sw.hip k_swt, k_sw_backtrack). Inputs as
  * acoss_sw_constrained. score_out: double[n_mats], may be NULL, acoss_sw_constrained's bit for bit.
  * seg_out: int32[4 n_mats] = (r0, c0, r1, c1) per matrix (may be NULL for acoss_sw_path). len_out:
  * int32[n_mats]; path_out: int32[n_mats][path_cap][2], the path's cells (r, c) first to last, the

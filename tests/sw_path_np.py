@@ -175,12 +175,16 @@ def make_matrix(M, N, density, plant, seed):
     return B
 
 
-# rows per lane and per band of the kernels (sw_path.hip): the tests assert that paths straddle both
+# rows per lane and per band of the kernels (sw.hip): the tests assert that paths straddle both
 LANE_ROWS, BAND_ROWS = 8, 512
 
 # (M, N, the rows a diagonal is planted at). 1030 x 40: one diagonal across each band boundary.
+# 530 x 24: the 16-row score kernel in one band with 34 of 64 lanes holding rows, the tracing DP in
+# two, a diagonal across row 512. 2050 x 24: the score kernel in three bands (boundaries at rows 1024
+# and 2048), the tracing DP in five, a diagonal across each of the score kernel's boundaries.
 SHAPES = [(3, 9, (2,)), (9, 3, (2,)), (4, 4, (2,)), (5, 9, (2,)), (14, 47, (2,)), (47, 14, (3,)), (33, 40, (2,)),
-          (64, 65, (5,)), (130, 70, (40,)), (260, 70, (150,)), (1030, 40, (500, 1005))]
+          (64, 65, (5,)), (130, 70, (40,)), (260, 70, (150,)), (1030, 40, (500, 1005)), (530, 24, (505,)),
+          (2050, 24, (1015, 2040))]
 DENSITIES = (0.1, 0.3, 0.6)
 
 # (M, N, density, plant): every shape at every density, bare and with each planted diagonal

@@ -1,4 +1,4 @@
-"""GPU parity of the acoss-side kernels (misc.hip, simple.hip) through the C-ABI.
+"""GPU parity of the acoss-side kernels (misc.hip, sw.hip, simple.hip) through the C-ABI.
 
 Checked against tests/golden/reference_golden.npz (outputs of the reference Python functions,
 tests/golden/make_golden.py) and against the C oracle (oracle/crp_oracle.cpp) on seeded inputs.

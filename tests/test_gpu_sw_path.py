@@ -1,5 +1,5 @@
 """GPU tests of the located and traced constrained Smith-Waterman alignment (acoss_sw_locate /
-acoss_sw_path: sw_path.hip k_swt<false>, k_swt<true>, k_sw_backtrack) against the numpy restatement
+acoss_sw_path: sw.hip k_swt<false>, k_swt<true>, k_sw_backtrack) against the numpy restatement
 tests/sw_path_np.py. Everything compares with `==`: scores, segments, lengths and paths; the score
 also with acoss_sw_constrained's."""
 import ctypes
@@ -59,6 +59,7 @@ def test_the_inputs_meet_the_hard_cases():
     assert any(lane), "a path across a lane boundary"
     assert any(sp.crosses_row(r, sp.BAND_ROWS) for _, r in got), "a path across row 512"
     assert any(sp.crosses_row(r, 2 * sp.BAND_ROWS) for _, r in got), "a path across row 1024"
+    assert any(sp.crosses_row(r, 4 * sp.BAND_ROWS) for _, r in got), "a path across row 2048"
     assert any(sp.tie_cells(B, r) for B, r in got), "a tie cell on a reported path"
     assert any(sp.miss_cells(B, r) for B, r in got), "a miss on a path"
     assert any(r.score == 0 for _, r in got) and any(len(r.path) == sp.path_bound(*B.shape) > 0 for B, r in got)
@@ -85,8 +86,9 @@ def test_small_sizes_share_waves():
 @pytest.mark.parametrize("shape", sp.SHAPES, ids=lambda s: "%dx%d" % s[:2])
 def test_each_shape_in_a_batch_of_its_own(shape):
     """The lanes per matrix follow the batch's largest row count: 1 (3 x 9) to 17 (130 x 70) lanes with
-    several matrices per wave, the whole wave from 260 rows on, three bands at 1030. The count is
-    no multiple of the matrices per wave."""
+    several matrices per wave, the whole wave from 260 rows on, three bands at 1030 and five at 2050;
+    the score kernel keeps 16 rows per lane from 530 rows on (one band there, three at 2050). The
+    count is no multiple of the matrices per wave."""
     M, N, _ = shape
     mats, want = _batch([c for c in sp.CASES if c[:2] == (M, N)], [(M, N)])
     LP = (M + 7) // 8

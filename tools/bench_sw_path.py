@@ -3,7 +3,8 @@ acoss_earlyfusion_path) against scoring alone (acoss_earlyfusion) on the same pa
 also written to profiles/sw_path/bench_sw_path.json.
 
     python tools/bench_sw_path.py [--warmup 2] [--repeats 5] [--short-tracks 2000] [--short-k 100]
-                                  [--no-blocks446] [--no-short] [--parent-lib libacoss_hip.so] [--out path.json]
+                                  [--no-blocks446] [--no-short] [--out path.json]
+                                  [--parent-lib libacoss_hip.so [--window-s 1.0] [--this-first]]
 
 The two EarlyFusion shapes the README quotes:
   blocks446: bench.py's EarlyFusion leg, 80 tracks of 446 beat blocks, all 3,160 unordered pairs
@@ -22,10 +23,16 @@ stage), the tracing DP ("dp_trace"), the direction DP ("dp_dir") and the backtra
 alone. The scores of the three routes must be equal bit for bit, the segments of locate and path
 equal, and every path must start and end on its segment; the run fails otherwise.
 
---parent-lib: a libacoss_hip.so built from the parent commit. Its acoss_earlyfusion and this tree's
-are then called alternately on the same pairs (same process, same buffers), --repeats times after
---warmup: the JSON holds both medians and each one's min..max spread, and says whether the medians
-agree within the larger spread.
+--parent-lib: a libacoss_hip.so built from the parent commit (same C-ABI). After the stages above,
+that library and this tree's are called alternately in one process on the same buffers:
+`earlyfusion`, `earlyfusion_locate` and `earlyfusion_path` on each shape. Every call is warmed on
+both libraries before any is timed (the parent's goes first in every round, this tree's with
+--this-first); a timed window is as many calls in a row as fill --window-s seconds, --repeats windows per
+library, then the same windows with the phase events on ("sw", "dp_trace", "dp_dir": the kernels
+alone). Per call and per phase the JSON ("parent_ab") holds every time, both medians, both min..max
+spreads and the verdict: this tree's median is no higher than the parent's plus the parent's own
+spread. The outputs of the two libraries must be equal and every verdict must hold; the run fails
+otherwise.
 """
 import argparse
 import json
@@ -73,43 +80,95 @@ def make_bank(rng, nbs):
             "max_blocks": int(nbs.max())}
 
 
-def parent_ab(a, bank, d_pairs, res_out):
-    """acoss_earlyfusion of the parent commit's library and of this tree's, alternately."""
+def _same(x, y):
+    import torch
+    if isinstance(x, dict):
+        return all(_same(x[k], y[k]) for k in x)
+    return bool(torch.equal(x, y))
+
+
+def ef_jobs(name, bank, d_pairs):
+    """The three EarlyFusion calls on one shape as (shape, call, fn(lib) -> output, phase keys)."""
+    from acoss import _lib
+
+    def via(fn):
+        def run(lib):
+            _lib._lib = lib  # the wrappers call through the handle load_library() returns
+            assert _lib.load_library() is lib
+            return fn(bank, d_pairs, KAPPA, K, MU)
+        return run
+    return [(name, "earlyfusion", via(_lib.earlyfusion), ("sw",)),
+            (name, "earlyfusion_locate", via(_lib.earlyfusion_locate), ("sw", "dp_trace")),
+            (name, "earlyfusion_path", via(_lib.earlyfusion_path), ("sw", "dp_dir"))]
+
+
+def _verdict(sm):
+    p, t = sm["parent"], sm["this"]
+    margin = p["max_s"] - p["min_s"]
+    diff = t["median_s"] - p["median_s"]
+    return {"parent": p, "this": t, "median_difference_s": round(diff, 7), "parent_spread_s": round(margin, 7),
+            "this_within_parent_spread": bool(diff <= margin),
+            "agree_within_larger_spread": bool(abs(diff) <= max(margin, t["max_s"] - t["min_s"]))}
+
+
+def parent_ab(a, jobs, res):
+    """The parent commit's library and this tree's, alternately, on every job. All jobs are warmed
+    first (the workspaces then have their final sizes); a timed window is `inner` calls in a row,
+    enough for --window-s seconds; then the same windows with the phase events on. Times are per call."""
     import torch
     from acoss import _lib
-    import ctypes
-    parent = ctypes.CDLL(os.path.abspath(a.parent_lib))  # it lacks the new entries: bind the one call
-    parent.acoss_earlyfusion.argtypes = _lib.SIGNATURES["acoss_earlyfusion"]
-    parent.acoss_earlyfusion.restype = ctypes.c_int
-    libs = {"parent": parent, "this": _lib.load_library()}
-    P = int(d_pairs.shape[0])
-    out = {k: torch.empty((P, 4), dtype=torch.float64, device="cuda") for k in libs}
-    args = (_lib._ptr(bank["mfccs"]), _lib._ptr(bank["ssms"]), _lib._ptr(bank["chromas"]), _lib._ptr(bank["chroma_med"]),
-            _lib._ptr(bank["off"]), _lib._ptr(bank["nb"]), int(bank["nb"].shape[0]), int(bank["max_blocks"]), 1000,
-            1225, 480, _lib._ptr(d_pairs), P, KAPPA, K, MU)
+    this = _lib.load_library()
+    libs = {"parent": _lib.load_library(os.path.abspath(a.parent_lib)), "this": this}
+    if a.this_first:  # the order inside every round; a second run in the other order shows what the order does
+        libs = {k: libs[k] for k in ("this", "parent")}
+    out, same_all, accepted = {}, True, True
+    try:
+        inner = []
+        for shape, call, fn, _ in jobs:
+            got = {}
+            for it in range(max(1, a.warmup)):
+                t1 = 0.0
+                for k, lib in libs.items():
+                    s, got[k] = _timed(lambda: fn(lib), torch)
+                    t1 = max(t1, s)
+            inner.append(max(1, int(np.ceil(a.window_s / t1))))
+            out["%s.%s" % (shape, call)] = {"calls_per_window": inner[-1], "same_output": _same(got["parent"], got["this"])}
+            del got
+        for (shape, call, fn, phases), n in zip(jobs, inner):
+            rec = out["%s.%s" % (shape, call)]
 
-    def call(k):
-        rc = libs[k].acoss_earlyfusion(*args, _lib._ptr(out[k]), _lib._stream())
-        if rc:
-            raise RuntimeError("acoss_earlyfusion (%s) returned %d" % (k, rc))
+            def window(lib):
+                for _ in range(n):
+                    fn(lib)
+            times = {k: [] for k in libs}
+            for _ in range(a.repeats):
+                for k, lib in libs.items():
+                    times[k].append(_timed(lambda: window(lib), torch)[0] / n)
+            rec.update(_verdict({k: _summary(v) for k, v in times.items()}))
+            ph = {key: {k: [] for k in libs} for key in phases}
+            for _ in range(a.repeats):
+                for k, lib in libs.items():
+                    _lib._lib = lib
+                    _lib.profile_enable(True)
+                    window(lib)
+                    torch.cuda.synchronize()
+                    got = _lib.profile_read()
+                    _lib.profile_enable(False)
+                    for key in phases:
+                        ph[key][k].append(got[key][0] * 1e-3 / n)
+            rec["phases"] = {key: _verdict({k: _summary(v) for k, v in ph[key].items()}) for key in phases}
+            same_all = same_all and rec["same_output"]
+            accepted = (accepted and rec["this_within_parent_spread"]
+                        and all(v["this_within_parent_spread"] for v in rec["phases"].values()))
+            log("parent A/B %s.%s: %s" % (shape, call, json.dumps(rec)))
+    finally:
+        _lib._lib = this
+    res["parent_ab"] = {"window_s": a.window_s, "order": list(libs), "rule": "this median <= parent median + parent's min..max spread",
+                        "calls": out, "same_outputs": same_all, "accepted": accepted}
+    res["ok"] = res.get("ok", True) and same_all and accepted
 
-    times = {k: [] for k in libs}
-    for it in range(a.warmup + a.repeats):
-        for k in libs:
-            s, _ = _timed(lambda: call(k), torch)
-            if it >= a.warmup:
-                times[k].append(s)
-    sm = {k: _summary(v) for k, v in times.items()}
-    spread = max(v["max_s"] - v["min_s"] for v in sm.values())
-    res_out["score_parent_vs_this"] = {
-        "parent": sm["parent"], "this": sm["this"], "spread_s": round(spread, 6),
-        "median_difference_s": round(sm["this"]["median_s"] - sm["parent"]["median_s"], 6),
-        "agree_within_spread": bool(abs(sm["this"]["median_s"] - sm["parent"]["median_s"]) <= spread),
-        "same_scores": bool(torch.equal(out["parent"], out["this"]))}
-    return bool(torch.equal(out["parent"], out["this"]))
 
-
-def stage(a, name, bank, pairs, res):
+def stage(a, name, bank, pairs, res, jobs):
     import torch
     from acoss import _lib
     # on the device and in the order the library runs them in, so the three calls and the parent's
@@ -164,8 +223,7 @@ def stage(a, name, bank, pairs, res):
     out["ratio_dp_trace_over_sw"] = round(ph_ms["locate_dp_trace_ms"] / ph_ms["score_sw_ms"], 2)
     out["ratio_dp_dir_over_dp_trace"] = round(ph_ms["path_dp_dir_ms"] / ph_ms["locate_dp_trace_ms"], 2)
     ok = scores_equal and seg_equal and ends_ok
-    if a.parent_lib:
-        ok = parent_ab(a, bank, d_pairs, out) and ok
+    jobs += ef_jobs(name, bank, d_pairs)
     res[name] = out
     res["ok"] = res.get("ok", True) and ok
     log("%s: %s" % (name, json.dumps(out)))
@@ -180,6 +238,8 @@ def main():
     ap.add_argument("--no-blocks446", dest="blocks446", action="store_false")
     ap.add_argument("--no-short", dest="short", action="store_false")
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--window-s", type=float, default=1.0)
+    ap.add_argument("--this-first", action="store_true")
     ap.add_argument("--seed", type=int, default=20250101)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sw_path", "bench_sw_path.json"))
     a = ap.parse_args()
@@ -190,16 +250,19 @@ def main():
     res = {"bench": "sw_path", "gpu": torch.cuda.get_device_name(0), "warmup": a.warmup, "repeats": a.repeats,
            "parent_lib": bool(a.parent_lib)}
     rng = np.random.Generator(np.random.PCG64(a.seed))
+    jobs = []
     if a.blocks446:
         NT = 80
         pairs = np.array([(i, j) for i in range(NT) for j in range(i + 1, NT)], np.int32)
-        stage(a, "blocks446", make_bank(rng, np.full(NT, 446)), pairs, res)
+        stage(a, "blocks446", make_bank(rng, np.full(NT, 446)), pairs, res, jobs)
     if a.short:
         n = a.short_tracks
         k = min(a.short_k, n - 1)
         cand = (np.arange(n)[:, None] + 1 + np.stack([rng.choice(n - 1, k, replace=False) for _ in range(n)])) % n
         pairs = np.stack([np.repeat(np.arange(n), k), cand.ravel()], 1).astype(np.int32)
-        stage(a, "short", make_bank(rng, rng.integers(14, 48, n)), pairs, res)
+        stage(a, "short", make_bank(rng, rng.integers(14, 48, n)), pairs, res, jobs)
+    if a.parent_lib:
+        parent_ab(a, jobs, res)
     line = json.dumps(res)
     print(line, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
